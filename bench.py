@@ -14,16 +14,25 @@ region ends after the last gather has completed, so every step's exchange is ins
 torch.distributed (gloo) is the control plane only: RCCL id broadcast, barriers, max over ranks.
 `--backend gloo` is the one-GPU rehearsal: ranks may share a device, records gathered via host.
 
-The roofline is the dominant kernel's: the library's launch timing (gjkepa_launch_timing: HIP events
+With `--full` the roofline is the dominant kernel's: the library's launch timing (gjkepa_launch_timing: HIP events
 recorded around every kernel launch, on the stream that launch goes to) gives each launch's duration
 inside the timed region; the kernel whose launches span the most time per step is dominant, and its
 `achieved` = algorithmic bytes of the pairs one launch serves (route tally) / its mean launch duration.
 The whole chain's figure is reported beside it (`roofline.chain`).
 
-Extra legs (not timed in `value`), rank 0 at N=1: configs C4 and C5 on the same GPU (throughput, their
-own dominant kernel, an oracle parity sample), fp32 compute, warm start, the host-buffer entry, and a
-CPU baseline — the oracle restatement (kind "port") over a bounded sample of the same pairs, which also
-re-checks GPU/CPU parity on that sample.
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the line:
+`value`, `ms_per_step` and the whole chain's roofline figure (HIP events around the timed steps).
+`--dump-outputs DIR` then also writes the last timed step's contact records, one `DIR/<field>.npy` per
+record field (float fields in the compute precision, integer fields as float64) plus `pair_index.npy`,
+the records' positions in the batch: every record of a batch of up to 2^18 pairs, a fixed seeded
+sample of 2^18 of a larger one (under 64 MB in all).  The batch is a function of the arguments alone.
+
+Everything else runs only with `--full` (none of it is timed in `value`): the launch-timing pass and
+the dominant kernel's roofline, the statistics of the records, and on rank 0 at N=1 the extra legs —
+configs C4 and C5 on the same GPU (throughput, their own dominant kernel, an oracle parity sample),
+fp32 compute, warm start, the host-buffer entry, and a CPU baseline — the oracle restatement (kind
+"port") over a bounded sample of the same pairs, which also re-checks GPU/CPU parity on that sample.
+At N > 1 `--full` adds the exchange's own check (verify_exchange).
 """
 from __future__ import annotations
 
@@ -177,6 +186,38 @@ def read_tally(ws) -> np.ndarray:
     return ws[4 * WS_COUNTERS:4 * (WS_COUNTERS + WS_TALLY)].cpu().numpy().view(np.uint32).copy()
 
 
+DUMP_MAX_PAIRS = 1 << 18    # fp64 records: 17 values of 8 bytes and pair_index, 144 B a pair: 36 MiB
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+DUMP_FIELDS = ("penetration_depth", "collision_normal", "collision_point", "nearest_points",
+               "collision", "colli_type", "status", "diag")
+
+
+def dump_sample(total: int) -> np.ndarray:
+    """Positions of the records --dump-outputs writes: all of a batch of up to DUMP_MAX_PAIRS, else a
+    fixed sample of that many (seeded by SEED, in ascending order)."""
+    if total <= DUMP_MAX_PAIRS:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(SEED).choice(total, DUMP_MAX_PAIRS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname: str, recs: np.ndarray) -> dict:
+    """Write the sampled records as dirname/<field>.npy (float fields as they are, integer fields as
+    float64) and dirname/pair_index.npy; returns what the line says about it."""
+    idx = dump_sample(len(recs))
+    sub = recs[idx]
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"pair_index": idx.astype(np.float64)}
+    for name in DUMP_FIELDS:
+        a = sub[name]
+        arrays[name] = np.ascontiguousarray(a if a.dtype.kind == "f" else a.astype(np.float64))
+    nbytes = sum(a.nbytes for a in arrays.values())
+    assert nbytes <= DUMP_MAX_BYTES, nbytes
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "records": int(len(idx)), "of": int(len(recs)), "bytes": int(nbytes),
+            "arrays": sorted(arrays)}
+
+
 def pmc_entry(precision: str, config: str, n: int, lib_src: str) -> dict | None:
     """The committed PMC summary of this (precision, config, batch) at the loaded library's source hash."""
     prof = os.path.join(ROOT, "profiles", "pmc_traffic.json")
@@ -303,11 +344,23 @@ def parse():
     ap.add_argument("--legs", default="C4,C5", help="N=1: extra configs run on the same GPU after the main one "
                                                    "(comma list; 'none' to skip)")
     ap.add_argument("--leg-sample", type=int, default=65536, help="pairs of each leg checked against the oracle")
-    ap.add_argument("--launch-timing", choices=["timed", "separate", "off"], default="separate",
-                    help="separate (default): the launch events in a second pass of the same steps right after the "
-                         "timed ones (they cost ~0.9%% on C2 when inside: profiles/r05/ab_launch_timing.txt); "
-                         "timed: inside the timed steps")
-    return ap.parse_args()
+    ap.add_argument("--launch-timing", choices=["timed", "separate", "off"], default=None,
+                    help="separate (default with --full): the launch events in a second pass of the same steps right "
+                         "after the timed ones (they cost ~0.9%% on C2 when inside: profiles/r05/ab_launch_timing.txt); "
+                         "timed: inside the timed steps; off (default without --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the launch-timing pass and the dominant "
+                         "kernel's roofline, record statistics, the fp32 / warm-start / host-buffer / CPU-baseline legs, "
+                         "configs C4 and C5, the oracle parity samples, and for N>1 the exchange's own check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's contact records as DIR/<field>.npy "
+                         "(rank 0; a fixed seeded sample of a batch above 2^18 pairs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.launch_timing is None:
+        args.launch_timing = "separate" if args.full else "off"
+    return args
 
 
 def run_leg(cfg: str, args, dev, stream, prec: int, lib_src: str) -> dict:
@@ -487,6 +540,11 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:            # what the last timed step left for its caller
+        last = (ex.last_gathered if ex else out).cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, last.view(gjkepa.record_dtype(prec)))
+        del last
     timing_ms_per_step = None
     if args.launch_timing == "separate":           # the same steps once more, with the launch events
         gjkepa.launch_timing(True)
@@ -509,12 +567,15 @@ def main():
     total_pairs = n * world
     value = total_pairs * args.steps / elapsed / 1e6
 
-    # statistics of the last step's records (rank-local)
-    recs = np.frombuffer((ex.last if ex else out).cpu().numpy().tobytes(), dtype=gjkepa.record_dtype(prec))
-    hit_rate = float((recs["collision"] != 0).mean())
-    status_counts = {int(k): int(v) for k, v in zip(*np.unique(recs["status"], return_counts=True))}
-    epa_iters = (recs["diag"] >> 8) & 0xFF
-    epa_mean = float(epa_iters[recs["collision"] != 0].mean()) if hit_rate > 0 else 0.0
+    # statistics of the last step's records (rank-local): --full, or when the launch timing needs them
+    recs, stats = None, {}
+    if args.full or lt is not None:
+        recs = np.frombuffer((ex.last if ex else out).cpu().numpy().tobytes(), dtype=gjkepa.record_dtype(prec))
+        hit_rate = float((recs["collision"] != 0).mean())
+        status_counts = {int(k): int(v) for k, v in zip(*np.unique(recs["status"], return_counts=True))}
+        epa_iters = (recs["diag"] >> 8) & 0xFF
+        epa_mean = float(epa_iters[recs["collision"] != 0].mean()) if hit_rate > 0 else 0.0
+        stats = {"hit_rate": round(hit_rate, 4), "epa_iters_mean": round(epa_mean, 2), "status_counts": status_counts}
 
     bpq = algorithmic_bytes_per_query(float(pool.hull_cnt.sum()) / n, 4, rec_bytes)
     achieved = n * bpq / (kern_ms * 1e-3) / 1e9
@@ -567,12 +628,14 @@ def main():
                    **({"exchange": exchange} if exchange else {})},
         "roofline": roofline,
         "dominant_kernel": dom,
-        "hit_rate": round(hit_rate, 4), "epa_iters_mean": round(epa_mean, 2), "status_counts": status_counts,
+        **stats,
         "lib": gjkepa.version_string(),
+        **({"outputs": dumped} if dumped else {}),
     }
+    extras = args.full and rank == 0 and world == 1      # the legs below: one GPU, --full only
 
     # fp32-compute side measurement (same batch), reported, never `value`
-    if rank == 0 and world == 1 and not args.no_f32_leg and prec == gjkepa.PREC_F64:
+    if extras and not args.no_f32_leg and prec == gjkepa.PREC_F64:
         out32 = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
         def l32():
             gjkepa.gjkepa_batch_device(args.version, 1.0, gjkepa.DTYPE_F32, gjkepa.PREC_F32, verts.data_ptr(),
@@ -603,7 +666,7 @@ def main():
 
     # warm start: frames alternate between the batch and a copy with every hull B moved
     # by 1e-3; each frame's warm slots seed the next.  Cold = the same frames through batch_device.
-    if rank == 0 and world == 1 and not args.no_warm_leg and prec == gjkepa.PREC_F64:
+    if extras and not args.no_warm_leg and prec == gjkepa.PREC_F64:
         moved = moved_copy(pool, 1e-3, SEED)
         frames = [verts, torch.from_numpy(moved).to(dev)]
         warm = torch.full((4 * n,), -1, dtype=torch.int32, device=dev)
@@ -633,7 +696,7 @@ def main():
 
     # host-buffer entry point (gjkepa_batch: H2D copy of hulls/pairs, kernels, D2H of records):
     # the PCIe-inclusive rate, reported beside `value`, never as it
-    if rank == 0 and world == 1 and not args.no_f32_leg:
+    if extras and not args.no_f32_leg:
         gjkepa.gjkepa_batch(pool, args.version, 1.0, precision=prec)
         t = time.perf_counter()
         for _ in range(2):
@@ -641,11 +704,11 @@ def main():
         result["host_api"] = {"value": round(2 * n / (time.perf_counter() - t) / 1e6, 3), "unit": "M queries/s",
                               "note": "gjkepa_batch on host buffers, PCIe transfers included"}
 
-    if dist and ex is not None:
+    if args.full and dist and ex is not None:
         verify_exchange(result, args, ex, comm, dist, world, rank, n, prec, rec_bytes, kern_ms_local,
                         (nmin, nmax, rmax), stream)
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if extras and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle  # checker / CPU baseline only
         m = min(args.cpu_sample, n) if args.cpu_sample > 0 else n
@@ -687,7 +750,7 @@ def main():
             result["parity_sample"] = {"pairs": m, "bitexact_records": float(eq.all(axis=1).mean()), "all_equal": bool(same)}
 
     # configs C4 / C5 on the same GPU, after everything above (N=1 only)
-    if rank == 0 and world == 1 and args.legs.lower() != "none":
+    if extras and args.legs.lower() != "none":
         result["legs"] = {}
         for cfg in [c.strip() for c in args.legs.split(",") if c.strip()]:
             if cfg in CONFIGS and cfg != args.config:

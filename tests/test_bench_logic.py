@@ -36,6 +36,42 @@ def test_busy_span_is_the_union_of_intervals():
     assert abs(bench.busy_span(rs) - (4.5 + 1.0)) < 1e-6
 
 
+def test_dump_outputs_writes_every_field_of_a_fixed_sample(tmp_path):
+    """--dump-outputs: one float .npy per record field; a batch above DUMP_MAX_PAIRS is cut to the same
+    seeded sample every time, named by pair_index, and the whole dump stays under the byte limit."""
+    n = bench.DUMP_MAX_PAIRS + 1000
+    rng = np.random.default_rng(1)
+    recs = np.zeros(n, gjkepa.REC64)
+    recs["penetration_depth"] = rng.random(n)
+    recs["collision_normal"] = rng.random((n, 3))
+    recs["nearest_points"] = rng.random((n, 6))
+    recs["collision"] = rng.integers(0, 2, n)
+    recs["diag"] = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    info = bench.dump_outputs(str(tmp_path / "a"), recs)
+    bench.dump_outputs(str(tmp_path / "b"), recs)
+    idx = np.load(tmp_path / "a" / "pair_index.npy")
+    assert len(idx) == bench.DUMP_MAX_PAIRS == info["records"] and info["of"] == n
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < n
+    ii = idx.astype(np.int64)
+    total = 0
+    for name in ("pair_index",) + bench.DUMP_FIELDS:
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float64 and a.tobytes() == b.tobytes(), name
+        total += a.nbytes
+        if name != "pair_index":
+            assert (a == recs[name][ii]).all(), name
+    assert total == info["bytes"] <= bench.DUMP_MAX_BYTES
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(x + ".npy" for x in info["arrays"])
+    # a small batch is written whole; fp32 records keep their float fields in float32
+    small = np.zeros(100, gjkepa.REC32)
+    small["penetration_depth"] = np.arange(100)
+    bench.dump_outputs(str(tmp_path / "c"), small)
+    d = np.load(tmp_path / "c" / "penetration_depth.npy")
+    assert d.dtype == np.float32 and (d == np.arange(100)).all()
+    assert np.load(tmp_path / "c" / "status.npy").dtype == np.float64
+    assert (np.load(tmp_path / "c" / "pair_index.npy") == np.arange(100)).all()
+
+
 def test_dominant_kernel_parts_and_pairs():
     n = 1000
     lt = np.concatenate(_chain(0, n) + _chain(1, n))

@@ -229,7 +229,7 @@ def test_two_rank_bench_verifies_its_exchange(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29541", os.path.join(root, "bench.py"),
            "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--pairs-per-gpu", "65536",
-           "--cpu-sample", "2048"]
+           "--cpu-sample", "2048", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
     line = [x for x in p.stdout.splitlines() if x.startswith("{")][-1]
@@ -253,7 +253,8 @@ def test_c3_whole_job_eight_ranks(tmp_path):
         else str(tmp_path / "c3_bench.log")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(C3_RANKS),
            "--master-addr", "127.0.0.1", "--master-port", "29553", os.path.join(ROOT, "bench.py"),
-           "--gpus", str(C3_RANKS), "--backend", "gloo", "--steps", "1", "--warmup", "0", "--cpu-sample", "2048"]
+           "--gpus", str(C3_RANKS), "--backend", "gloo", "--steps", "1", "--warmup", "0", "--cpu-sample", "2048",
+           "--full"]
     _log("C3: 8-rank bench starting")
     with open(log, "w") as lf:
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=lf, text=True, timeout=400, env=env, cwd=str(tmp_path))

@@ -4,8 +4,8 @@
 # Steps (each under its own time limit; the session stops at the first failure):
 #   tests[=EXPR]   -m gpu suite (pytest -k EXPR when given)
 #   smoke          __graft_entry__.smoke()
-#   bench          the default bench.py line, as the driver runs it
-#   lines          bench.py --config C2 / C4 / C5 lines (10 steps)
+#   bench          the default bench.py --full line (every leg)
+#   lines          bench.py --full --config C2 / C4 / C5 lines (10 steps)
 #   prof           rocprofv3 --kernel-trace --stats of C2 / C4 / C5 bench commands
 #   pmc            PMC passes (one counter group per rocprofv3 run) for C2 / C4 / C5
 #   ab=R:CFGS:V1,V2  A/B of library variants (tools/build_variant.sh) against the in-tree build,
@@ -36,17 +36,17 @@ step_tests() {
   local rc=$?; tail -3 $OUT/pytest_gpu.log; return $rc
 }
 step_smoke() { timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 && cat $OUT/smoke.log; }
-step_bench() { timeout -k 10 500 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err && cat $OUT/bench_default.json; }
+step_bench() { timeout -k 10 500 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err && cat $OUT/bench_default.json; }
 step_lines() {
   for c in C2 C4 C5; do
-    timeout -k 10 400 python bench.py --config $c --steps 10 --warmup 3 --legs none > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -5 $OUT/bench_$c.err; return 1; }
+    timeout -k 10 400 python bench.py --full --config $c --steps 10 --warmup 3 --legs none > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -5 $OUT/bench_$c.err; return 1; }
     python3 -c "import json;d=json.load(open('$OUT/bench_$c.json'));print('$c',d['value'],d['ms_per_step'],d['roofline'].get('traffic'),d.get('parity_sample',{}).get('all_equal'))"
   done
 }
 step_prof() {
   for c in C2 C4 C5; do
     local s=5; [ $c != C2 ] && s=3
-    timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_$c -o run --output-format csv -- python3 bench.py --config $c --steps $s --warmup 1 --legs none $BQ > $OUT/prof_$c.json 2> $OUT/prof_$c.err || { echo "prof $c failed"; tail -5 $OUT/prof_$c.err; return 1; }
+    timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_$c -o run --output-format csv -- python3 bench.py --full --config $c --steps $s --warmup 1 --legs none $BQ > $OUT/prof_$c.json 2> $OUT/prof_$c.err || { echo "prof $c failed"; tail -5 $OUT/prof_$c.err; return 1; }
     echo "prof $c ok"
   done
 }
@@ -69,7 +69,7 @@ step_ab() {
       local lib=$D/libgjkepa_hip.so
       [ "$v" != main ] && lib=$D/variants/$v/libgjkepa_hip.so
       for c in ${cfgs//,/ }; do
-        GJKEPA_LIB=$lib timeout -k 10 240 python bench.py --config $c --legs none --cpu-sample 65536 --no-f32-leg --no-warm-leg --launch-timing off \
+        GJKEPA_LIB=$lib timeout -k 10 240 python bench.py --full --config $c --legs none --cpu-sample 65536 --no-f32-leg --no-warm-leg --launch-timing off \
           > $OUT/ab_${v}_${c}_$r.json 2>> $OUT/ab.err || { echo "FAIL $v $c"; tail -5 $OUT/ab.err; return 1; }
         echo "$r $v $c $(python3 -c "import json;d=json.loads(open('$OUT/ab_${v}_${c}_$r.json').read().splitlines()[-1]);print(d['value'], d['ms_per_step'], d.get('parity_sample',{}).get('all_equal'))")"
       done
@@ -83,7 +83,7 @@ step_envab() {
   for r in $(seq 1 $rounds); do
     for v in ${vals//,/ }; do
       for c in ${cfgs//,/ }; do
-        env $var=$v timeout -k 10 240 python bench.py --config $c --legs none --cpu-sample 65536 --no-f32-leg --no-warm-leg --launch-timing off \
+        env $var=$v timeout -k 10 240 python bench.py --full --config $c --legs none --cpu-sample 65536 --no-f32-leg --no-warm-leg --launch-timing off \
           > $OUT/envab_${v}_${c}_$r.json 2>> $OUT/envab.err || { echo "FAIL $var=$v $c"; tail -5 $OUT/envab.err; return 1; }
         echo "$r $var=$v $c $(python3 -c "import json;d=json.loads(open('$OUT/envab_${v}_${c}_$r.json').read().splitlines()[-1]);print(d['value'], d['ms_per_step'], d.get('parity_sample',{}).get('all_equal'))")"
       done
@@ -103,7 +103,7 @@ step_stamps() {
   done
 }
 step_gloo2() {
-  timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --backend gloo --steps 3 --warmup 1 --pairs-per-gpu 262144 > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err && cat $OUT/bench_2rank_gloo.json
+  timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --backend gloo --steps 3 --warmup 1 --pairs-per-gpu 262144 > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err && cat $OUT/bench_2rank_gloo.json
 }
 step_hull() {
   timeout -k 10 300 python -u -m pytest tests/test_hull.py -x -v -m gpu --timeout 120 --timeout-method thread > $OUT/hull_pytest.log 2>&1 || { tail -5 $OUT/hull_pytest.log; return 1; }
