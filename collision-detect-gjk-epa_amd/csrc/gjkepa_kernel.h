@@ -179,8 +179,25 @@
 #ifndef GJKEPA_EPA_SEED
 #define GJKEPA_EPA_SEED 1           // refill tiers: a fresh pair's iteration 1 joins the common support step (epa_seed)
 #endif
+// Seed hand-over (fp64 compute only).  A GJK hit from the tetrahedron code leaves, beside the simplex
+// codes, the four unit face normals of its final simplex in the pair's record slot, and a flag that
+// says whether EPA may take them:
+//   words 0-3   simplex vertex codes       word 4   GJK iterations       word 5   park slot + 1
+//   words 6-29  four normals of 3 doubles in EPA seed-face order [1,2,3],[1,3,4],[1,2,4],[2,3,4]
+//   word 30     1: normals valid (every face normalised, no zero component) and the simplex is
+//               hull_build's first tetrahedron (four distinct points, non-degenerate at the hull
+//               epsilon); 0 otherwise.  Written for every hit.
+// EPA's iteration 1 computes exactly these normals (UNINML's cross has both operands of GJK's negated:
+// the same products, the same norm, the same bits but for the sign of a zero component, which is why
+// a normal with one is not handed), so a fresh pair with the flag set reads its quad
+// lane's normal, skips the tetrahedron tests and normalises only the two outward faces whose winding
+// it swaps.  The words stay intact until the pair's EPA has finished (a deferral writes nothing, parking
+// writes word 5), so a pair restarted by a later tier seeds from them again.  0: EPA recomputes (A/B).
+#ifndef GJKEPA_SEED_HANDOFF
+#define GJKEPA_SEED_HANDOFF 1
+#endif
 #ifndef GJKEPA_GJK_META
-#define GJKEPA_GJK_META 1           // GJK tiers load every routed pair's hull counts / offsets once per chunk (0: per pair, A/B)
+#define GJKEPA_GJK_META 1          // GJK tiers load every routed pair's hull counts / offsets once per chunk (0: per pair, A/B)
 #endif
 #ifndef GJKEPA_CONTACT_META
 #define GJKEPA_CONTACT_META 1       // contact tiers load every routed pair's hull counts / offsets once per chunk (0: per pair, A/B)
@@ -289,6 +306,10 @@
 // support gap is open, or an fp32 error status) are recomputed whole in fp64 by the redo launch at
 // the end of the chain (gjkepa_kernel.hip "fp32 certificate")
 #define GJKEPA_ROUTE_REDO 0x2E
+// two tally words that are no route codes: fresh pairs (not resumed from a park slot) an EPA tier
+// seeded from GJK's handed normals, and fresh pairs it seeded by its own arithmetic
+#define GJKEPA_TALLY_SEED_OWN 0x2D
+#define GJKEPA_TALLY_SEED_HANDED 0x2F
 
 // Polytope parking.  EPA tiers 2 and 3 hand a pair whose polytope is about to outgrow them to tier 4
 // with its polytope instead of its GJK simplex: the state at the start of an iteration (vertices,

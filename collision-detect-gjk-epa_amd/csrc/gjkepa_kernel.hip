@@ -78,6 +78,45 @@ template <typename T> DEV bool redo_status(int r, bool last_tier) {
     return r == ST_REDO || r == GJKEPA_STATUS_EPA_MAXITER || r == GJKEPA_STATUS_DEGENERATE || (r == ST_DEFER && last_tier);
 }
 
+// seed hand-over (gjkepa_kernel.h, GJKEPA_SEED_HANDOFF): fp64 compute only, the fp64 record slot has the room
+template <typename T> DEV constexpr bool handoff() { return GJKEPA_SEED_HANDOFF != 0 && sizeof(T) == 8; }
+constexpr int kSeedNmlWord = 6, kSeedFlagWord = 30;     // record-slot words: normals (24 words), flag
+// what GJK hands EPA with a hit: this quad lane's raw face normal of the final simplex (GJK face order)
+// and whether EPA may seed from the quad's normals
+template <typename T> struct SeedOut {
+    V3<T> nq;
+    bool ok;
+};
+// what a fresh EPA pair read back: its quad lane's seed-face normal (EPA seed order), if `on`
+template <typename T> struct SeedIn {
+    V3<T> nq;
+    bool on;
+};
+template <typename T> DEV SeedIn<T> no_seed() { return SeedIn<T>{zero3<T>(), false}; }
+// a fresh pair's flag and its quad lane's normal, loaded beside the simplex codes
+template <typename T> DEV SeedIn<T> load_seed(const uint32_t* slot, int gl) {
+    SeedIn<T> h = no_seed<T>();
+    if constexpr (handoff<T>()) {
+        const T* np = reinterpret_cast<const T*>(slot + kSeedNmlWord) + 3 * (gl & 3);
+        h.nq = vmk<T>(np[0], np[1], np[2]);
+        h.on = slot[kSeedFlagWord] == 1u;
+    }
+    return h;
+}
+// hull_build's tetrahedron search (the first non-degenerate one in list order) gives the simplex itself,
+// points (0, 1, 2, 3): four distinct points, non-degenerate at the hull epsilon
+template <typename T, typename GR> DEV bool simplex_is_first_tetra(const GR& g, V3<T> s0, V3<T> s1, V3<T> s2, V3<T> s3) {
+    const bool distinct = !veq(s1, s0) && !veq(s2, s0) && !veq(s2, s1) && !veq(s3, s0) && !veq(s3, s1) && !veq(s3, s2);
+    if (!g.unib(distinct)) return false;
+    const V3<T> e1 = vsub(s1, s0);
+    const T l1 = norm2(e1);
+    if (!g.unib(l1 > Tol<T>::HULL)) return false;
+    const V3<T> c2 = cross(e1, vsub(s2, s0));
+    if (!g.unib(norm2(c2) / l1 > Tol<T>::HULL)) return false;
+    const V3<T> pn = utzvec(c2);
+    return g.unib(fabs(dot(vsub(s3, s0), pn)) > Tol<T>::HULL);
+}
+
 // GET_RANDOM_UNIT_VECTOR table (:1578-1689)
 [[maybe_unused]] static __constant__ double kDirTab[100][3] = {
 #include "dirtab.inc"
@@ -968,7 +1007,7 @@ template <typename T, int R> struct EpaState {
 };
 #define EPAST_T EpaState<T, (FC + G - 1) / G>
 
-CTX_T DEV int epa_begin(CTX& c, EPAST_T& S, V3<T> s0, V3<T> s1, V3<T> s2, V3<T> s3) {
+CTX_T DEV int epa_begin(CTX& c, EPAST_T& S, V3<T> s0, V3<T> s1, V3<T> s2, V3<T> s3, SeedIn<T> h = no_seed<T>()) {
     constexpr int R = (FC + G - 1) / G;
     auto& E = c.L.u.e;
     const V3<T> O = zero3<T>();
@@ -984,8 +1023,11 @@ CTX_T DEV int epa_begin(CTX& c, EPAST_T& S, V3<T> s0, V3<T> s1, V3<T> s2, V3<T> 
     // builds face q (its first vertex is the distance reference), the quad shares the results
     const int fq = gl & 3;
     const V3<T> fa = fq == 3 ? s1 : s0, fb = (fq == 0 || fq == 2) ? s1 : s2, fc = fq == 0 ? s2 : s3;
-    const V3<T> nq = uninml(fa, fb, fc);
-    if (c.g.unib(quad_any(is_zero_nml(nq)))) return GJKEPA_STATUS_DEGENERATE;
+    V3<T> nq = h.nq;                                          // handed: GJK's normal of this face, the same bits
+    if (!h.on) {
+        nq = uninml(fa, fb, fc);
+        if (c.g.unib(quad_any(is_zero_nml(nq)))) return GJKEPA_STATUS_DEGENERATE;
+    }
     const T dq = fabs(dot(vsub(O, fa), nq));
     const T d0 = qbcast<0>(dq), d1 = qbcast<1>(dq), d2 = qbcast<2>(dq), d3 = qbcast<3>(dq);
     T minv = d0;                                              // MINLOC, first index
@@ -1038,21 +1080,13 @@ CTX_T DEV int epa_begin(CTX& c, EPAST_T& S, V3<T> s0, V3<T> s1, V3<T> s2, V3<T> 
 // adds the support point(s) as hull_build adds them, in the same pass as the other groups' steps.
 // ST_FALLBACK: the tetrahedron is not the simplex (duplicate or near-degenerate points): epa_begin.
 constexpr int ST_FALLBACK = 102;
-CTX_T DEV int epa_seed(CTX& c, EPAST_T& S, V3<T> s0, V3<T> s1, V3<T> s2, V3<T> s3) {
+CTX_T DEV int epa_seed(CTX& c, EPAST_T& S, V3<T> s0, V3<T> s1, V3<T> s2, V3<T> s3, SeedIn<T> h = no_seed<T>()) {
     constexpr int R = (FC + G - 1) / G;
     auto& E = c.L.u.e;
     const V3<T> O = zero3<T>();
     const int gl = c.g.gl;
-    // hull_build's tetrahedron search (first non-degenerate one in list order) must give (0, 1, 2, 3)
-    const bool distinct = !veq(s1, s0) && !veq(s2, s0) && !veq(s2, s1) && !veq(s3, s0) && !veq(s3, s1) && !veq(s3, s2);
-    if (!c.g.unib(distinct)) return ST_FALLBACK;
-    const V3<T> e1 = vsub(s1, s0);
-    const T l1 = norm2(e1);
-    if (!c.g.unib(l1 > Tol<T>::HULL)) return ST_FALLBACK;
-    const V3<T> c2 = cross(e1, vsub(s2, s0));
-    if (!c.g.unib(norm2(c2) / l1 > Tol<T>::HULL)) return ST_FALLBACK;
-    const V3<T> pn = utzvec(c2);
-    if (!c.g.unib(fabs(dot(vsub(s3, s0), pn)) > Tol<T>::HULL)) return ST_FALLBACK;
+    // hull_build's tetrahedron search must give (0, 1, 2, 3); handed normals: GJK made the same tests
+    if (!h.on && !simplex_is_first_tetra(c.g, s0, s1, s2, s3)) return ST_FALLBACK;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         free_slot(S.F, r);
@@ -1063,8 +1097,11 @@ CTX_T DEV int epa_seed(CTX& c, EPAST_T& S, V3<T> s0, V3<T> s1, V3<T> s2, V3<T> s
     // seed soup [1,2,3],[1,3,4],[1,2,4],[2,3,4] (:279-293) on the quad lanes, as in epa_begin
     const int fq = gl & 3;
     const V3<T> fa = fq == 3 ? s1 : s0, fb = (fq == 0 || fq == 2) ? s1 : s2, fc = fq == 0 ? s2 : s3;
-    const V3<T> nq = uninml(fa, fb, fc);
-    if (c.g.unib(quad_any(is_zero_nml(nq)))) return GJKEPA_STATUS_DEGENERATE;
+    V3<T> nq = h.nq;                                          // handed: GJK's normal of this face, the same bits
+    if (!h.on) {
+        nq = uninml(fa, fb, fc);
+        if (c.g.unib(quad_any(is_zero_nml(nq)))) return GJKEPA_STATUS_DEGENERATE;
+    }
     const T dq = fabs(dot(vsub(O, fa), nq));
     const T d0 = qbcast<0>(dq), d1 = qbcast<1>(dq), d2 = qbcast<2>(dq), d3 = qbcast<3>(dq);
     T minv = d0;                                              // MINLOC, first index
@@ -1099,9 +1136,14 @@ CTX_T DEV int epa_seed(CTX& c, EPAST_T& S, V3<T> s0, V3<T> s1, V3<T> s2, V3<T> s
         V3<T> Pb = vsel(gl == 0 || gl == 2, s1, s2);
         V3<T> Pd = vsel(gl == 0, s2, s3);
         const V3<T> n0 = cross(vsub(Pb, Pa), vsub(Pd, Pb));
-        if (dot(n0, vsub(Pa, cen)) < T(0)) { int t = b; b = d; d = t; const V3<T> q = Pb; Pb = Pd; Pd = q; }
-        const V3<T> n = uninml(Pa, Pb, Pd);
-        bad = is_zero_nml(n);
+        const bool swap = dot(n0, vsub(Pa, cen)) < T(0);
+        if (swap) { int t = b; b = d; d = t; const V3<T> q = Pb; Pb = Pd; Pd = q; }
+        // (Pa, Pb, Pd) unswapped is this lane's seed triple (fa, fb, fc): its normal is nq, never zero when handed
+        V3<T> n = nq;
+        if (!h.on || swap) {
+            n = uninml(Pa, Pb, Pd);
+            bad = is_zero_nml(n);
+        }
         S.F.nx[0] = n.x; S.F.ny[0] = n.y; S.F.nz[0] = n.z;
         S.F.d[0] = dot(vsub(zero3<T>(), Pa), n);
         S.F.fv[0] = (uint32_t)a | ((uint32_t)b << 8) | ((uint32_t)d << 16);
@@ -1304,14 +1346,15 @@ CTX_T DEV void epa_resume(CTX& c, EPAST_T& S, const unsigned char* rec, uint32_t
 // value with a flag, not as a maybe-null pointer: a pointer to the caller's copy selected against null
 // keeps that copy in scratch memory (one 32-byte store per lane and pair).
 CTX_T DEV int epa(CTX& c, V3<T> s0, V3<T> s1, V3<T> s2, V3<T> s3, T& depth, V3<T>& normal, int& iters, int& nf,
-                  bool park = false, ParkCtl pk = {}, const unsigned char* rec = nullptr, uint32_t* gjk_it = nullptr) {
+                  bool park = false, ParkCtl pk = {}, const unsigned char* rec = nullptr, uint32_t* gjk_it = nullptr,
+                  SeedIn<T> h = no_seed<T>()) {
     EPAST_T S;
     int st;
     if (rec) {
         epa_resume(c, S, rec, *gjk_it);
         st = epa_grow(c, S, false);
     } else {
-        st = epa_begin(c, S, s0, s1, s2, s3);     // iteration 1 up to its hull; it closes in the loop
+        st = epa_begin(c, S, s0, s1, s2, s3, h);  // iteration 1 up to its hull; it closes in the loop
         if (st == 0) st = ST_CONT;
     }
     while (st == ST_CONT) {
@@ -1858,8 +1901,10 @@ CTX_T DEV bool warm_start(CTX& c, const uint32_t* w, uint32_t* kc) {
     return true;
 }
 
-// Sphere pre-test + GJK.  Returns PH_MISS, PH_HIT (codes k0..k3 filled) or an error status.
-CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, bool try_axis = false) {
+// Sphere pre-test + GJK.  Returns PH_MISS, PH_HIT (codes k0..k3 filled) or an error status.  With `so`
+// (seed hand-over), a hit also returns this quad lane's face normal of the final simplex and whether
+// EPA may seed from the quad's normals.
+CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, bool try_axis = false, SeedOut<T>* so = nullptr) {
     const V3<T> O = zero3<T>();
     auto& L = c.L;
     const int gl = c.g.gl;
@@ -1957,6 +2002,7 @@ CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, bool try_axis = false
     const T vd = dot(vsub(O, s2), dir);
     bool enter = false;
     if (c.g.unib(fabs(vd) < Tol<T>::PT) && c.g.unib(inside_tri(s0, s1, s2, O))) enter = true;
+    const bool tri = enter;  // hit on the initial triangle: no fourth point, no face normals
     const int q = gl & 3;
     V3<T> nq = zero3<T>();   // this quad lane's raw face normal of the current simplex
     T mdq = 0;
@@ -2019,19 +2065,33 @@ CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, bool try_axis = false
         GK_STAMP(SG_CHK);
     }
     kc[0] = k0; kc[1] = k1; kc[2] = k2; kc[3] = k3;
+    if constexpr (handoff<T>()) {
+        if (so) {
+            // EPA's UNINML divides where a component of the raw cross exceeds Tol::Z, quad_normal where the
+            // norm does: a norm above 4 Z has a component above 4 Z / sqrt(3) > 2 Z, so both divide (and by
+            // the same norm).  UNINML's cross has both operands negated, so every nonzero product and sum is
+            // the same, but a zero can come out with the other sign (a - b and b - a are both +0 where the
+            // coordinates are equal): only normals without a zero component are the same bits.  Then the
+            // tests epa_seed would make on the same four points.
+            const bool same_bits = c.g.unib(quad_all(mdq > T(4) * Tol<T>::Z && nq.x != T(0) && nq.y != T(0) && nq.z != T(0)));
+            so->nq = nq;
+            so->ok = !tri && same_bits && simplex_is_first_tetra(c.g, s0, s1, s2, s3);
+        }
+    }
     return PH_HIT;
 }
 
 // EPA_solu's polytope loop (:274-323) from the GJK simplex: 0 (depth, n filled), an error
 // status or ST_DEFER; `diag_epa` gets (epa_iters << 8) | (faces << 16).
 CTX_T DEV int epa_phase(CTX& c, const uint32_t* kc, T& depth, V3<T>& n, uint32_t& diag_epa, bool park = false,
-                        ParkCtl pk = {}, const unsigned char* rec = nullptr, uint32_t* gjk_it = nullptr) {
+                        ParkCtl pk = {}, const unsigned char* rec = nullptr, uint32_t* gjk_it = nullptr,
+                        SeedIn<T> h = no_seed<T>()) {
     V3<T> s0 = zero3<T>(), s1 = s0, s2 = s0, s3 = s0;
     if (!rec) { s0 = decode_pt(c, kc[0]); s1 = decode_pt(c, kc[1]); s2 = decode_pt(c, kc[2]); s3 = decode_pt(c, kc[3]); }
     depth = 0;
     n = zero3<T>();
     int eit = 0, nf = 0;
-    const int st = epa(c, s0, s1, s2, s3, depth, n, eit, nf, park, pk, rec, gjk_it);
+    const int st = epa(c, s0, s1, s2, s3, depth, n, eit, nf, park, pk, rec, gjk_it, h);
     diag_epa = ((uint32_t)(eit & 0xff) << 8) | ((uint32_t)(nf & 0xffff) << 16);
     return st;
 }
@@ -2379,8 +2439,9 @@ __global__ __launch_bounds__(64, MINW) void gjk_kernel(const gjkepa_gjk_args a) 
                 if constexpr (WARM) {    // a pair that missed last call runs the reference GJK again
                     if (a.warm[4 * pair] != kWarmMiss) warm_hit = warm_start(c, a.warm + 4 * pair, kc);
                 }
+                SeedOut<T> so{zero3<T>(), false};     // a warm-start hit hands nothing over
                 if (warm_hit) r = PH_HIT;
-                else r = gjk_phase(c, kc, gjk_it, GJKEPA_AXIS_REJECT != 0);
+                else r = gjk_phase(c, kc, gjk_it, GJKEPA_AXIS_REJECT != 0, &so);
                 __builtin_amdgcn_wave_barrier();
                 GK_STAMP(SG_CHK);
                 if (WARM && gl < 4)     // this call's simplex seeds the next call; a miss mark; none for errors
@@ -2392,6 +2453,17 @@ __global__ __launch_bounds__(64, MINW) void gjk_kernel(const gjkepa_gjk_args a) 
                         const int j = j0 + gl;
                         const uint32_t word = j == 0 ? kc[0] : j == 1 ? kc[1] : j == 2 ? kc[2] : j == 3 ? kc[3] : j == 4 ? (uint32_t)gjk_it : 0u;
                         if (j < 6) reinterpret_cast<uint32_t*>(a.out)[pair * (sizeof(T) == 8 ? 32 : 16) + j] = word;
+                    }
+                    if constexpr (handoff<T>()) {
+                        // the quad's normals in EPA seed order (GJK faces 0..3 are seed faces 1, 2, 0, 3) and
+                        // the flag, for every hit: the slot may hold an earlier record's bytes
+                        uint32_t* slot = reinterpret_cast<uint32_t*>(a.out) + pair * 32;
+                        if (so.ok && gl < 4) {
+                            const int f = gl == 0 ? 1 : gl == 1 ? 2 : gl == 2 ? 0 : 3;
+                            T* np = reinterpret_cast<T*>(slot + kSeedNmlWord) + 3 * f;
+                            np[0] = so.nq.x; np[1] = so.nq.y; np[2] = so.nq.z;
+                        }
+                        if (gl == 0) slot[kSeedFlagWord] = so.ok ? 1u : 0u;
                     }
                     next = (uint8_t)(GJKEPA_ROUTE_EPA0 + epa_tier_for(na > nb ? na : nb));
                 } else if (r == PH_MISS) {
@@ -2463,9 +2535,13 @@ __global__ __launch_bounds__(64, MINW) void epa_kernel(const gjkepa_epa_args a) 
         uint32_t it_park = gjk_it;
         const ParkCtl pk{a.park, a.park_ctr, a.park_cap, gjk_it, slot};
         const bool can_park = (PR & 1) && a.park && a.next_code >= 0;
-        const int r = (c.na > G * K || c.nb > G * K) ? ST_DEFER
+        const bool fits = c.na <= G * K && c.nb <= G * K;
+        // read after the hull load, not beside it: tier 3 has no registers to carry it across (128 VGPRs)
+        const SeedIn<T> seed = load_seed<T>(slot, gl);
+        if (fits && !parked && gl == 0) tally_route(seed.on ? GJKEPA_TALLY_SEED_HANDED : GJKEPA_TALLY_SEED_OWN);
+        const int r = !fits ? ST_DEFER
                     : epa_phase(c, kc, depth, n, de, can_park, pk,
-                                parked ? a.park + (size_t)(parked - 1) * GJKEPA_PARK_BYTES : nullptr, &it_park);
+                                parked ? a.park + (size_t)(parked - 1) * GJKEPA_PARK_BYTES : nullptr, &it_park, seed);
 #endif
         __builtin_amdgcn_wave_barrier();
         const uint32_t diag = (gjk_it & 0xffu) | de;
@@ -2613,18 +2689,20 @@ __global__ __launch_bounds__(64, MINW) void epa_kernel_refill(const gjkepa_epa_a
             uint32_t kc[4];
             kc[0] = slot[0]; kc[1] = slot[1]; kc[2] = slot[2]; kc[3] = slot[3];
             gjk_it = slot[4];
+            const SeedIn<T> seed = load_seed<T>(slot, gl);
             load_hulls(c, verts + a.hull_off[ha], verts + a.hull_off[hb]);
             S.iters = 1; S.nf = 0;
             int r = ST_DEFER;
             seeded = false;
             if (c.na <= G * K && c.nb <= G * K) {
                 const V3<T> s0 = decode_pt(c, kc[0]), s1 = decode_pt(c, kc[1]), s2 = decode_pt(c, kc[2]), s3 = decode_pt(c, kc[3]);
+                if (gl == 0) tally_route(seed.on ? GJKEPA_TALLY_SEED_HANDED : GJKEPA_TALLY_SEED_OWN);
 #if GJKEPA_EPA_SEED
-                r = epa_seed(c, S, s0, s1, s2, s3);
+                r = epa_seed(c, S, s0, s1, s2, s3, seed);
                 seeded = r == 0;
                 if (r == ST_FALLBACK)
 #endif
-                    r = epa_begin(c, S, s0, s1, s2, s3);
+                    r = epa_begin(c, S, s0, s1, s2, s3, seed);
             }
             __builtin_amdgcn_wave_barrier();
             active = r == 0;

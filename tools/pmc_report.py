@@ -80,7 +80,8 @@ def main():
         # which a wave had a VALU instruction issuing; against 1024 SIMDs x kernel time x 2.4 GHz
         "valu_busy_frac": tot["SQ_ACTIVE_INST_VALU"] * 4.0 / (1024 * secs * 2.4e9) if secs and tot["SQ_ACTIVE_INST_VALU"] else None,
         "kernels": kernels,
-        "source": f"tools/gpu_session.sh pmc run {tag}, kernels summed over their dispatches per chain (one chain = one GJK tier-0 dispatch), summed over the chain",
+        # the session and config of the passes (session tag / pmc_<config>), not where the results were kept
+        "source": f"tools/gpu_session.sh pmc run {'/'.join(os.path.normpath(tag).split(os.sep)[-2:])}, kernels summed over their dispatches per chain (one chain = one GJK tier-0 dispatch), summed over the chain",
     }
     path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
     allj = json.load(open(path)) if os.path.exists(path) else {}
