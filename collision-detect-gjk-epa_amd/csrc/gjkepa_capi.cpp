@@ -125,7 +125,7 @@ int num_cus_current() {
     return cus;
 }
 
-// Second stream for the overlapped contact passes (GJKEPA_CONTACT_OVERLAP).  The pairs EPA tier t
+// Second stream for the overlapped contact passes.  The pairs EPA tier t
 // finishes carry the route codes GJKEPA_ROUTE_CT(t) + contact tier, and their contact pass is forked
 // onto an internal stream as soon as tier t is done, so it runs beside EPA tiers t+1..4: on C2 the
 // contact pass of EPA tier 0 (most of the hits) overlaps tier 1 (a few long pairs), on C5 that of
@@ -503,7 +503,7 @@ int enqueue(int32_t version, double tol_ff, int32_t vert_dtype, int32_t precisio
     // launches cost more latency than the overlap saves
     Fork* f = nullptr;
     int rc;
-    if (GJKEPA_CONTACT_OVERLAP && n_pairs >= kOverlapMin && (rc = fork_state(s, &f))) return rc;
+    if (n_pairs >= kOverlapMin && (rc = fork_state(s, &f))) return rc;
     const bool overlap = f != nullptr;
     // EPA tiers 2 and 3 side by side (not when a contact pass forks after tier 3)
     const bool e23 = overlap && e23_streams() == 2 && !((GJKEPA_FORK_MASK >> 3) & 1);

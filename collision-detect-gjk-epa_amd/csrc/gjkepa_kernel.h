@@ -62,7 +62,7 @@
 #define GJKEPA_E0_FCAP 64
 #endif
 #ifndef GJKEPA_E0_MINW
-#define GJKEPA_E0_MINW 3        // with GJKEPA_E0_LH: 168 VGPRs; with GJKEPA_EPA_HPACK the LDS holds 12 waves/CU
+#define GJKEPA_E0_MINW 3        // with GJKEPA_E0_LH: 168 VGPRs; with the packed horizon list the LDS holds 12 waves/CU
 #endif
 #ifndef GJKEPA_E0_REFILL
 #define GJKEPA_E0_REFILL 2      // refill a wave's groups once this many are idle (0: per-round kernel)
@@ -176,9 +176,6 @@
 #ifndef GJKEPA_C1_MINW
 #define GJKEPA_C1_MINW 3        // A/B r5 (2 rounds): 2 -> 3 waves/SIMD C4 39.9 -> 40.6, C5 23.1 -> 23.5 M/s, C2 unchanged
 #endif
-#ifndef GJKEPA_EPA_SEED
-#define GJKEPA_EPA_SEED 1           // refill tiers: a fresh pair's iteration 1 joins the common support step (epa_seed)
-#endif
 // Seed hand-over (fp64 compute only).  A GJK hit from the tetrahedron code leaves, beside the simplex
 // codes, the four unit face normals of its final simplex in the pair's record slot, and a flag that
 // says whether EPA may take them:
@@ -196,53 +193,12 @@
 #ifndef GJKEPA_SEED_HANDOFF
 #define GJKEPA_SEED_HANDOFF 1
 #endif
-#ifndef GJKEPA_GJK_META
-#define GJKEPA_GJK_META 1          // GJK tiers load every routed pair's hull counts / offsets once per chunk (0: per pair, A/B)
-#endif
-#ifndef GJKEPA_CONTACT_META
-#define GJKEPA_CONTACT_META 1       // contact tiers load every routed pair's hull counts / offsets once per chunk (0: per pair, A/B)
-#endif
 #ifndef GJKEPA_E1_PRIO
 #define GJKEPA_E1_PRIO 2            // wave priority (s_setprio) of EPA tier 1's waves (0: default; A/B r5: C2 +0.2%, C5 +0.6%)
-#endif
-#ifndef GJKEPA_HORIZON_W16
-#define GJKEPA_HORIZON_W16 1        // horizon twin test on 16-bit edge windows (0: byte compares; A/B r5: C2 +0.6%, C4 +1.6%, C5 +2.2%)
-#endif
-#ifndef GJKEPA_SCREEN_SINGLE
-#define GJKEPA_SCREEN_SINGLE 1      // fp32 support screen: a group's single candidate is the answer, no fp64 dot (A/B r5: C4 +1.0%, C2 +0.2%)
-#endif
-#ifndef GJKEPA_EPA_HPACK
-#define GJKEPA_EPA_HPACK 1          // one-word horizon edges, FC / 2 of them, where keys fit 16 bits (0: A/B r5 C2 157.3 -> 162.7)
-#endif
-#ifndef GJKEPA_PAD_V0
-#define GJKEPA_PAD_V0 1             // hull slots past the count hold vertex 0 again; support scans skip the mask
-                                    // (A/B r6, 3 rounds: C2 +1.1%, C4 +1.6%, C5 +1.9%; 0: masked)
-#endif
-#ifndef GJKEPA_EMPTY_INF
-#define GJKEPA_EMPTY_INF 1          // free polytope face slots carry a -inf distance; MINLOC without validity masks
-                                    // (A/B r6, 3 rounds: C2 +3.4%, C4 +1.7%, C5 +2.7%; 0: masked scan)
-#endif
-#ifndef GJKEPA_DOTS_FMAX
-#define GJKEPA_DOTS_FMAX 1          // support_dots' per-lane maximum on v_max_f64 (0: compare + selects, A/B)
-#endif
-#ifndef GJKEPA_EPA_PLACE
-#define GJKEPA_EPA_PLACE 1          // EPA new faces built on the lane that owns their slot (0: staged in LDS, A/B)
-#endif
-#ifndef GJKEPA_LDS_SKEW
-#define GJKEPA_LDS_SKEW 1           // pad LDS coordinate columns and skew group images across banks (0: A/B off)
-#endif
-#ifndef GJKEPA_HULL_AOS
-#define GJKEPA_HULL_AOS 0           // 1: LDS hull copy as one (x, y, z, 0) 16-byte record per vertex (A/B: EPA tier 0 +13%, GJK +7%: bank conflicts)
 #endif
 #ifndef GJKEPA_SCREEN_MIN_K
 #define GJKEPA_SCREEN_MIN_K 8       // fp32-screened support mapping in tiers with K >= this (fp64 compute,
 #endif                              // fp32 storage); 0 = off
-#ifndef GJKEPA_AXIS_REJECT
-#define GJKEPA_AXIS_REJECT 0        // diagnostic A/B only, never the product build: GJK answers "miss"
-                                    // when the centre axis separates the hulls.  Not parity-safe: the
-                                    // reference's tetra loop reports hits on separated hulls through
-                                    // isPointInSimplex's on-face branch (:1246-1256)
-#endif
 // Per tier: hull vertices read from the group's LDS copy (1) instead of held in registers (0).
 // The LDS form frees 6K VGPRs per lane: EPA tier 0 then fits three waves per SIMD (168 VGPRs)
 // without spills (C2: EPA tier 0 6.10 -> 5.26 ms); GJK tier 0 is +1% either way.  Measured and
@@ -281,9 +237,6 @@
 #ifndef GJKEPA_C1_LH
 #define GJKEPA_C1_LH 1
 #endif
-#ifndef GJKEPA_CONTACT_OVERLAP
-#define GJKEPA_CONTACT_OVERLAP 1    // each EPA tier's contact pass on a second stream, overlapping the later EPA tiers
-#endif
 #define GJKEPA_GJK_TIERS 3
 #define GJKEPA_EPA_TIERS 6
 #define GJKEPA_CONTACT_TIERS 2
@@ -300,7 +253,8 @@
 #define GJKEPA_ROUTE_GJK1 1         // + GJK tier - 1 (tiers 1, 2)
 #define GJKEPA_ROUTE_EPA0 0x10      // + EPA tier
 #define GJKEPA_ROUTE_CT0 0x20       // + contact tier
-// with GJKEPA_CONTACT_OVERLAP, the pairs EPA tier t finishes go to contact tier c under code CT(t) + c
+// each EPA tier's contact pass runs on a second stream, overlapping the later EPA tiers: the pairs
+// EPA tier t finishes go to contact tier c under code CT(t) + c
 #define GJKEPA_ROUTE_CT(t) (GJKEPA_ROUTE_CT0 + 2 * (t))
 // fp32 compute: pairs whose fp32 answer is not certified (EPA's MINLOC distance dropped or its final
 // support gap is open, or an fp32 error status) are recomputed whole in fp64 by the redo launch at
@@ -318,9 +272,6 @@
 // (the same arithmetic, so the same bits).  Results are those of a restart: the keys carry the face
 // order, and a polytope does not depend on where its faces sit.  When the park slots run out a pair
 // restarts from the simplex as before.
-#ifndef GJKEPA_PARK
-#define GJKEPA_PARK 1                 // 0: restart from the simplex (A/B)
-#endif
 #define GJKEPA_PARK_VC 72             // largest polytope parked: tier 2's (tier 3's is 40 / 64)
 #define GJKEPA_PARK_FC 128
 #define GJKEPA_PARK_HDR 128           // header: counters (64 B) and direction / distances (<= 64 B)

@@ -189,18 +189,16 @@ enum { SG_LOAD = 0, SG_SPHERE, SG_INIT, SG_UPD, SG_CHK, SG_STORE, SG_ROUTE,
 // VC == 0 is the GJK kernel (FC == 0) or the contact kernel (FC == 1), which carry only their own
 // scratch, so a 16-pair GJK wave does not pay for polytope or contact arrays.
 // FUSED: the one-kernel query path (query_kernel) keeps the contact arrays beside the polytope.
-// One hull vertex in LDS (GJKEPA_HULL_AOS): x, y, z and a zero pad, so a lane fetches a whole
-// vertex with one ds_read_b128 (fp32 storage) instead of three ds_read_b32 from three columns.
-template <typename TH> struct alignas(16) HV { TH x, y, z, w; };
-
+// The hull copy is three coordinate columns per hull; one 16-byte (x, y, z, 0) record per vertex lost
+// to bank conflicts (A/B: EPA tier 0 +13%, GJK +7%).
 template <typename T, typename TH, int G, int K, int VC_, int FC_, bool FUSED = false> struct Lds {
     static constexpr int NH = G * K;
     // Coordinate columns are NH + 1 elements apart, so the six columns (hull A/B x, y, z) start on
     // six different banks: the sphere test reads element i of all six at once (one lane each).
-    static constexpr int NHP = NH + GJKEPA_LDS_SKEW;
-    static constexpr int VC = VC_ > 0 ? VC_ : 1, FC = VC_ > 0 ? FC_ : 1, GS = VC_ > 0 && !GJKEPA_EPA_PLACE ? G : 1;
+    static constexpr int NHP = NH + 1;
+    static constexpr int VC = VC_ > 0 ? VC_ : 1, FC = VC_ > 0 ? FC_ : 1;
     static constexpr int NC = ((VC_ == 0 && FC_ == 1) || FUSED) ? NH : 1;
-    // Horizon list packing (GJKEPA_EPA_HPACK): a horizon edge is one word u | w << HVB | key << 2 HVB
+    // Horizon list packing (A/B r5: C2 157.3 -> 162.7): a horizon edge is one word u | w << HVB | key << 2 HVB
     // (HVB bits per vertex id) where every face key fits the rest (kbase grows by at most 3 FC per hull
     // insertion, two insertions per iteration, <= 100 iterations), and the list holds FC / 2 edges
     // (hull_add defers a pair whose horizon is longer: at most VC edges, so only tiers with VC > FC / 2
@@ -208,14 +206,10 @@ template <typename T, typename TH, int G, int K, int VC_, int FC_, bool FUSED = 
     // then fit a twelfth wave per CU.  Tiers whose polytopes are larger than that and whose occupancy
     // is set by registers (1 and 2, 72 / 128) keep the two-word list: packed, C5 lost 0.9%.
     static constexpr int HVB = VC_ <= 128 ? 7 : 8;
-    static constexpr bool HPACK = GJKEPA_EPA_HPACK && VC_ > 0 && VC_ <= (1 << HVB) && (VC_ <= 40 || 2 * VC_ <= FC_) &&
+    static constexpr bool HPACK = VC_ > 0 && VC_ <= (1 << HVB) && (VC_ <= 40 || 2 * VC_ <= FC_) &&
                                   4 + 600LL * FC_ < (1LL << (32 - 2 * HVB));
     static constexpr int HC = HPACK ? FC / 2 : FC;
-#if GJKEPA_HULL_AOS
-    HV<TH> hv[2][NH];                       // hull A (0) / B (1) vertex i, storage precision
-#else
     TH hx[2][NHP], hy[2][NHP], hz[2][NHP];  // hull A (0) / B (1) vertices, storage precision
-#endif
     struct None {};
     struct E {                           // EPA polytope (faces themselves are in registers)
             T vx[VC], vy[VC], vz[VC];    // vertices by id
@@ -226,10 +220,6 @@ template <typename T, typename TH, int G, int K, int VC_, int FC_, bool FUSED = 
                 struct H {                                                                 // hull_add lists
                     uint64_t visl[FC];                       // visible faces: ids | key << 32
                     uint32_t horu[HC], hork[HPACK ? 1 : FC]; // horizon edges: u | w << 8 (| new face key << 16 if HPACK), new face key
-#if !GJKEPA_EPA_PLACE
-                    T sn[GS][4];                             // new faces of one round: normal, |distance|
-                    uint32_t sv[GS], sk[GS];                 //   ids, key
-#endif
                 } h;
                 struct S { T srt[FC]; } s;                                                 // sorted_equal
                 struct O { uint32_t key[FC]; uint32_t ord[FC]; } o;                       // centroid order
@@ -250,21 +240,11 @@ template <typename T, typename TH, int G, int K, int VC_, int FC_, bool FUSED = 
 // the 32 four-byte banks, so group g's lane l and group g+1's lane l, touching the same field, hit
 // different banks; an unpadded image size is often a multiple of 16 or 32 dwords, which puts every
 // group of a half on the same banks (GJK tier 0: 16 groups, 8 per half, two distinct bank offsets).
-// With GJKEPA_HULL_AOS the images are 16-byte aligned and, for G < 16, skewed by 4G dwords modulo
-// 64 banks: the G lanes of a group read G consecutive 16-byte vertex records, so the 16-lane groups
-// of a ds_read_b128 (16 / G groups) then cover 256 distinct bytes of banks.
 template <typename L_t, int G> constexpr size_t lds_stride() {
-    if constexpr (GJKEPA_HULL_AOS) {
-        size_t dw = (sizeof(L_t) + 15) / 16 * 4;            // 16-byte aligned, in dwords
-        if (GJKEPA_LDS_SKEW && G < 16)
-            while (dw % 64 != (size_t)(4 * G)) dw += 4;
-        return dw * 4;
-    } else {
-        size_t dw = (sizeof(L_t) + 7) / 8 * 2;              // 8-byte aligned, in dwords
-        if (GJKEPA_LDS_SKEW && G < 32)                      // dw = G x odd (mod 32): the 32 / G groups
-            while ((dw % 32) % G != 0 || ((dw % 32) / G) % 2 == 0) dw += 2;   // of a half on distinct banks
-        return dw * 4;
-    }
+    size_t dw = (sizeof(L_t) + 7) / 8 * 2;              // 8-byte aligned, in dwords
+    if (G < 32)                                         // dw = G x odd (mod 32): the 32 / G groups
+        while ((dw % 32) % G != 0 || ((dw % 32) / G) % 2 == 0) dw += 2;   // of a half on distinct banks
+    return dw * 4;
 }
 
 template <typename T, typename TH, int G, int K, int VC, int FC, int LH> struct Ctx {
@@ -280,23 +260,8 @@ template <typename T, typename TH, int G, int K, int VC, int FC, int LH> struct 
     T bx[kRegHull ? K : 1], by[kRegHull ? K : 1], bz[kRegHull ? K : 1];
     int na, nb;
     float vmax_a = 0, vmax_b = 0;   // largest |coordinate| of each hull (fp32 support screen)
-#if GJKEPA_HULL_AOS
-    // vertex i of hull h in storage precision, fetched whole (one 16-byte LDS read for fp32)
-    DEV V3<TH> raw(int h, int i) const {
-        if constexpr (sizeof(TH) == 4) {
-            typedef float f4 __attribute__((ext_vector_type(4)));
-            const f4 v = *reinterpret_cast<const f4*>(&L.hv[h][i]);
-            return vmk<TH>(v.x, v.y, v.z);
-        } else {
-            const HV<TH> v = L.hv[h][i];
-            return vmk<TH>(v.x, v.y, v.z);
-        }
-    }
-    DEV TH rawc(int h, int i, int ax) const { return ax == 0 ? L.hv[h][i].x : ax == 1 ? L.hv[h][i].y : L.hv[h][i].z; }
-#else
     DEV V3<TH> raw(int h, int i) const { return vmk<TH>(L.hx[h][i], L.hy[h][i], L.hz[h][i]); }
     DEV TH rawc(int h, int i, int ax) const { return ax == 0 ? L.hx[h][i] : ax == 1 ? L.hy[h][i] : L.hz[h][i]; }
-#endif
     DEV V3<T> A(int i) const { const V3<TH> v = raw(0, i); return vmk<T>((T)v.x, (T)v.y, (T)v.z); }
     DEV V3<T> B(int i) const { const V3<TH> v = raw(1, i); return vmk<T>((T)v.x, (T)v.y, (T)v.z); }
     // this lane's k-th vertex (k*G + gl) of hull A / B as a whole vector
@@ -332,17 +297,14 @@ template <int K> struct ScreenOn {
 CTX_T DEV void screened_idx(const CTX& c, V3<T> d, int h, float vmax, int& out) {
     const float fx = (float)d.x, fy = (float)d.y, fz = (float)d.z;
     const float sg = h ? -1.0f : 1.0f;
-    const int n = h ? c.nb : c.na;
     float sv[K];
     float m = -FLT_MAX;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const int i = k * G + c.g.gl;
-        // GJKEPA_PAD_V0: slots past the count hold vertex 0 again, whose screen value can only make
-        // vertex 0's duplicates candidates too (then the full path below takes the lowest index)
-        const V3<TH> v = c.raw(h, GJKEPA_PAD_V0 || i < n ? i : 0);
-        const float t = sg * fmaf(fz, v.z, fmaf(fy, v.y, fx * v.x));
-        sv[k] = GJKEPA_PAD_V0 || i < n ? t : -FLT_MAX;
+        // no mask by the count: slots past it hold vertex 0 again (load_hulls), whose screen value can only
+        // make vertex 0's duplicates candidates too (then the full path below takes the lowest index)
+        const V3<TH> v = c.raw(h, k * G + c.g.gl);
+        sv[k] = sg * fmaf(fz, v.z, fmaf(fy, v.y, fx * v.x));
         m = fmaxf(m, sv[k]);
     }
     m = gmax<G>(m);
@@ -352,19 +314,16 @@ CTX_T DEV void screened_idx(const CTX& c, V3<T> d, int h, float vmax, int& out) 
     const float thr = bnd >= 0x1p-90f ? m - 0x1p-18f * bnd : -INFINITY;
     uint32_t cand = 0;
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int i = k * G + c.g.gl;
-        if ((GJKEPA_PAD_V0 || i < n) && !(sv[k] < thr)) cand |= 1u << k;      // NaN threshold or value: candidate
-    }
-    if constexpr (GJKEPA_SCREEN_SINGLE) {
-        // one candidate in the whole group (the usual case): it is the fp64 argmax, so its index is
-        // the answer without its fp64 dot or the fp64 group reduction (an int group min only)
-        const uint64_t lanes = c.g.ballot(cand != 0);
-        if (!c.g.any(__builtin_popcount(cand) > 1) && popc(lanes) <= 1) {
-            const int key = gmin<G>(cand ? (int)__builtin_ctz(cand) * G + c.g.gl : 0x7FFFFFFF);
-            out = c.g.uni(key == 0x7FFFFFFF ? 0 : key);
-            return;
-        }
+    for (int k = 0; k < K; ++k)
+        if (!(sv[k] < thr)) cand |= 1u << k;      // NaN threshold or value: candidate
+    // one candidate in the whole group (the usual case): it is the fp64 argmax, so its index is
+    // the answer without its fp64 dot or the fp64 group reduction (an int group min only;
+    // A/B r5: C4 +1.0%, C2 +0.2%)
+    const uint64_t lanes = c.g.ballot(cand != 0);
+    if (!c.g.any(__builtin_popcount(cand) > 1) && popc(lanes) <= 1) {
+        const int key = gmin<G>(cand ? (int)__builtin_ctz(cand) * G + c.g.gl : 0x7FFFFFFF);
+        out = c.g.uni(key == 0x7FFFFFFF ? 0 : key);
+        return;
     }
     T best = -Tol<T>::BIG;
     int bi = 0x7FFFFFFF;
@@ -382,24 +341,16 @@ CTX_T DEV void screened_idx(const CTX& c, V3<T> d, int h, float vmax, int& out) 
 }
 
 // This lane's dots with one direction d over both hulls: t[0][k] = d.a_(kG+gl), t[1][k] = -(d.b_(kG+gl))
-// (= (-d).b bit for bit up to a zero's sign), -BIG past the hull, and the group maxima m[0], m[1]:
+// (= (-d).b bit for bit up to a zero's sign) and the group maxima m[0], m[1]:
 // get_nearest_points' argmax values, and get_info_collisionType's / the contact points' HUGE-start
 // max scans (:381, :401, :471-472) for the same direction.
 template <typename T, int K> struct DotSet { T t[2][K]; T m[2]; };
 
-// GJKEPA_PAD_V0: the hull slots past a hull's count hold copies of its vertex 0 (load_hulls), whose dot
-// can tie only with vertex 0 itself at a higher index, so the lowest-index argmax and the maxima are the
-// plain scan's without masking the padding (three VALU per vertex and hull); the contact band sets,
-// which count members, still mask by index.
-CTX_T DEV T dot_slot(int i, int n, T t) {
-    if constexpr (GJKEPA_PAD_V0) return t;
-    else return i < n ? t : -Tol<T>::BIG;
-}
-// this lane's running maximum of the dots: v_max_f64 (red_max) instead of compare + two selects
-template <typename T> DEV T dots_max(T t, T v) {
-    if constexpr (GJKEPA_DOTS_FMAX) return red_max(t, v);
-    else return t > v ? t : v;
-}
+// The hull slots past a hull's count hold copies of its vertex 0 (load_hulls), whose dot can tie only
+// with vertex 0 itself at a higher index, so the lowest-index argmax and the maxima are the plain scan's
+// without masking the padding (three VALU per vertex and hull; A/B r6, 3 rounds: C2 +1.1%, C4 +1.6%,
+// C5 +1.9%); the contact band sets, which count members, still mask by index.  The lane's running
+// maximum is v_max_f64 (red_max) instead of compare + two selects.
 CTX_T DEV void support_dots(const CTX& c, V3<T> d, DotSet<T, K>& D, int& ia, int& ib) {
     T (&ta)[K] = D.t[0];
     T (&tb)[K] = D.t[1];
@@ -407,28 +358,25 @@ CTX_T DEV void support_dots(const CTX& c, V3<T> d, DotSet<T, K>& D, int& ia, int
     if constexpr (GJKEPA_DOTS_FENCE_MIN_G > 0 && G >= GJKEPA_DOTS_FENCE_MIN_G && K >= 4 && VC > 0) {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const int i = k * G + c.g.gl;
         const V3<T> a = c.AV(k);
-        ta[k] = dot_slot<T, TH, G, K, VC, FC, LH>(i, c.na, d.x * a.x + d.y * a.y + d.z * a.z);
-        va = dots_max(ta[k], va);
+        ta[k] = d.x * a.x + d.y * a.y + d.z * a.z;
+        va = red_max(ta[k], va);
     }
     gk_lds_fence();                      // hull B's vertices are read after hull A's dots
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const int i = k * G + c.g.gl;
         const V3<T> b = c.BV(k);
-        tb[k] = dot_slot<T, TH, G, K, VC, FC, LH>(i, c.nb, -(d.x * b.x + d.y * b.y + d.z * b.z));
-        vb = dots_max(tb[k], vb);
+        tb[k] = -(d.x * b.x + d.y * b.y + d.z * b.z);
+        vb = red_max(tb[k], vb);
     }
     } else {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const int i = k * G + c.g.gl;
         const V3<T> a = c.AV(k), b = c.BV(k);
-        ta[k] = dot_slot<T, TH, G, K, VC, FC, LH>(i, c.na, d.x * a.x + d.y * a.y + d.z * a.z);
-        tb[k] = dot_slot<T, TH, G, K, VC, FC, LH>(i, c.nb, -(d.x * b.x + d.y * b.y + d.z * b.z));
-        va = dots_max(ta[k], va);
-        vb = dots_max(tb[k], vb);
+        ta[k] = d.x * a.x + d.y * a.y + d.z * a.z;
+        tb[k] = -(d.x * b.x + d.y * b.y + d.z * b.z);
+        va = red_max(ta[k], va);
+        vb = red_max(tb[k], vb);
     }
     }
     va = gmax<G>(va);
@@ -561,11 +509,14 @@ template <typename T, int R> struct Faces {
 };
 #define FACES_T Faces<T, (FC + G - 1) / G>
 
-// A free slot: kEmpty, and with GJKEPA_EMPTY_INF a distance of -inf, so that |d| = +inf never wins MINLOC
-// and dot(p, n) + d never passes the visibility test: the MINLOC scan needs no validity mask
+// A free slot: kEmpty and a distance of -inf, so that |d| = +inf never wins MINLOC and dot(p, n) + d
+// never passes the visibility test: the MINLOC scan needs no validity mask (A/B r6, 3 rounds: C2 +3.4%,
+// C4 +1.7%, C5 +2.7%).
+// Invariant: a slot becomes empty only through free_slot, the one writer of kEmpty; that is what keeps
+// a stale |d| out of MINLOC (face_argmin scans d[] of every slot and never looks at fv[]).
 template <typename T, int R> DEV void free_slot(Faces<T, R>& F, int r) {
     F.fv[r] = kEmpty;
-    if constexpr (GJKEPA_EMPTY_INF) F.d[r] = -__builtin_inf();
+    F.d[r] = -__builtin_inf();
 }
 
 template <typename T> DEV T qnan() { return __builtin_nan(""); }
@@ -615,9 +566,9 @@ CTX_T DEV int hull_add(CTX& c, FACES_T& F, uint32_t& kbase, int& hw, int& nv, in
             if (!live[r]) continue;
             if (c.g.bit(vm[r])) {
                 vp[r] = base + mbcnt(vm[r]);
-                // GJKEPA_HORIZON_W16: v0 repeated in byte 3, so the face's three directed edges are
-                // the 16-bit windows at bytes 0, 1 and 2 (v0v1, v1v2, v2v0)
-                const uint32_t fw = GJKEPA_HORIZON_W16 ? F.fv[r] | ((F.fv[r] & 0xffu) << 24) : F.fv[r];
+                // v0 repeated in byte 3, so the face's three directed edges are the 16-bit windows at
+                // bytes 0, 1 and 2 (v0v1, v1v2, v2v0; against byte compares A/B r5: C2 +0.6%, C4 +1.6%, C5 +2.2%)
+                const uint32_t fw = F.fv[r] | ((F.fv[r] & 0xffu) << 24);
                 E.x.h.visl[vp[r]] = (uint64_t)fw | ((uint64_t)F.key[r] << 32);
             }
             base += popc(vm[r]);
@@ -642,23 +593,13 @@ CTX_T DEV int hull_add(CTX& c, FACES_T& F, uint32_t& kbase, int& hw, int& nv, in
             const uint32_t w = (fv >> (8 * (s == 2 ? 0 : s + 1))) & 0xffu;
             bool twin = false;
             int rank = 0;
-            if constexpr (GJKEPA_HORIZON_W16) {
-                // the twin (w, u) is a directed edge of face j iff it is one of its three 16-bit windows
-                const uint32_t t = w | (u << 8);
-                for (int j = 0; j < nvis; ++j) {
-                    const uint64_t qj = E.x.h.visl[j];
-                    const uint32_t q = (uint32_t)qj;
-                    twin = twin || (q & 0xffffu) == t || ((q >> 8) & 0xffffu) == t || (q >> 16) == t;
-                    rank += (uint32_t)(qj >> 32) < kk;
-                }
-            } else {
-                for (int j = 0; j < nvis; ++j) {
-                    const uint64_t qj = E.x.h.visl[j];
-                    const uint32_t q = (uint32_t)qj;
-                    const uint32_t q0 = q & 0xffu, q1 = (q >> 8) & 0xffu, q2 = (q >> 16) & 0xffu;
-                    twin = twin || (q0 == w && q1 == u) || (q1 == w && q2 == u) || (q2 == w && q0 == u);
-                    rank += (uint32_t)(qj >> 32) < kk;
-                }
+            // the twin (w, u) is a directed edge of face j iff it is one of its three 16-bit windows
+            const uint32_t t = w | (u << 8);
+            for (int j = 0; j < nvis; ++j) {
+                const uint64_t qj = E.x.h.visl[j];
+                const uint32_t q = (uint32_t)qj;
+                twin = twin || (q & 0xffffu) == t || ((q >> 8) & 0xffffu) == t || (q >> 16) == t;
+                rank += (uint32_t)(qj >> 32) < kk;
             }
             hz = !twin;
             uw = u | (w << L_t::HVB);
@@ -688,7 +629,6 @@ CTX_T DEV int hull_add(CTX& c, FACES_T& F, uint32_t& kbase, int& hw, int& nv, in
     }
     __builtin_amdgcn_wave_barrier();
     GK_STAMP(SE_CMP);
-#if GJKEPA_EPA_PLACE
     // New faces (horizon edge h coned to k) are built on the lane whose slot receives them, straight
     // into its face registers.  Placement does not change results (the keys carry the order).  The
     // visible faces' slots are freed first; each round, the group lanes that still have a free slot
@@ -727,73 +667,6 @@ CTX_T DEV int hull_add(CTX& c, FACES_T& F, uint32_t& kbase, int& hw, int& nv, in
     }
     top = gmax<G>(top);
     hw = hw > top ? hw : top;
-#else
-    // New faces (horizon edge h coned to k) are built G at a time on group lane h % G and staged
-    // in LDS, then copied into their slots.  Placement (results do not depend on it: the keys
-    // carry the order): new face h takes the slot of visible face h, the ones beyond nvis are
-    // appended at the high-water mark hw; a visible slot left over becomes a hole.  When the
-    // append would pass FC, the new faces take the first nh free slots (holes included).
-    const V3<T> P = c.vert(k);
-    bool bad = false;
-    int tj[R];               // index of the new face this slot receives, -1 if none
-    const int app = nh - nvis;
-    if (hw + (app > 0 ? app : 0) <= FC) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int slot = r * G + gl;
-            int h = vp[r];
-            if (h < 0 && slot >= hw && slot < hw + app) h = nvis + slot - hw;
-            tj[r] = h < nh ? h : -1;
-            if (vp[r] >= 0) free_slot(F, r);
-        }
-        if (app > 0) hw += app;
-    } else {
-        int fbase = 0, top = 0;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const bool vis = vp[r] >= 0;
-            const bool fre = ((F.fv[r] & kEmpty) || vis) && (r * G + gl < FC);
-            const uint64_t fm = c.g.ballot(fre);
-            const int fr = fbase + mbcnt(fm);
-            fbase += popc(fm);
-            tj[r] = fre && fr < nh ? fr : -1;
-            if (tj[r] >= 0) top = r * G + gl + 1;
-            if (vis) free_slot(F, r);
-        }
-        top = gmax<G>(top);
-        hw = hw > top ? hw : top;
-    }
-    for (int h0 = 0; h0 < nh; h0 += G) {
-        const int h = h0 + gl;
-        if (h < nh) {
-            const uint32_t uw = E.x.h.horu[h];
-            constexpr uint32_t vm_ = (1u << L_t::HVB) - 1u;
-            const int u = (int)(uw & vm_), w = (int)((uw >> L_t::HVB) & vm_);
-            const V3<T> U = c.vert(u), W = c.vert(w);
-            const V3<T> n = uninml(U, W, P);
-            bad = bad || is_zero_nml(n);
-            E.x.h.sn[gl][0] = n.x; E.x.h.sn[gl][1] = n.y; E.x.h.sn[gl][2] = n.z;
-            E.x.h.sn[gl][3] = dot(vsub(zero3<T>(), U), n);
-            E.x.h.sv[gl] = (uint32_t)u | ((uint32_t)w << 8) | ((uint32_t)k << 16);
-            E.x.h.sk[gl] = L_t::HPACK ? uw >> (2 * L_t::HVB) : E.x.h.hork[h];
-        }
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int j = tj[r] - h0;
-            const bool tgt = j >= 0 && j < G;
-            if (__ballot(tgt)) {
-                if (tgt) {
-                    F.nx[r] = E.x.h.sn[j][0]; F.ny[r] = E.x.h.sn[j][1]; F.nz[r] = E.x.h.sn[j][2];
-                    F.d[r] = E.x.h.sn[j][3];
-                    F.fv[r] = E.x.h.sv[j];
-                    F.key[r] = E.x.h.sk[j];
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-#endif
     GK_STAMP(SE_CONE);
     nf = nf2;
     if (c.g.any(bad)) return GJKEPA_STATUS_DEGENERATE;
@@ -865,27 +738,15 @@ CTX_T DEV void face_argmin(CTX& c, const FACES_T& F, T& dmin, V3<T>& n, bool& ne
     T v = Tol<T>::BIG;
     uint32_t kk = 0xFFFFFFFFu;
     int rr = -1;
-    T vmin;
-    if constexpr (GJKEPA_EMPTY_INF) {
-        // free slots hold |d| = +inf: the value-only minimum over every row, then this lane's lowest key
-        // among its rows at the group minimum
+    // free slots hold |d| = +inf (free_slot): the value-only minimum over every row, then this lane's
+    // lowest key among its rows at the group minimum
 #pragma unroll
-        for (int r = 0; r < R; ++r) v = red_min(fabs(F.d[r]), v);
-        vmin = gmin<G>(v);
+    for (int r = 0; r < R; ++r) v = red_min(fabs(F.d[r]), v);
+    const T vmin = gmin<G>(v);
 #pragma unroll
-        for (int r = 0; r < R; ++r)
-            if (fabs(F.d[r]) == vmin && F.key[r] < kk) { kk = F.key[r]; rr = r; }
-        v = vmin;
-    } else {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const bool valid = !(F.fv[r] & kEmpty);
-            if (!__ballot(valid)) continue;
-            const T ad = fabs(F.d[r]);
-            if (valid && (ad < v || (ad == v && F.key[r] < kk))) { v = ad; kk = F.key[r]; rr = r; }
-        }
-        vmin = gmin<G>(v);
-    }
+    for (int r = 0; r < R; ++r)
+        if (fabs(F.d[r]) == vmin && F.key[r] < kk) { kk = F.key[r]; rr = r; }
+    v = vmin;
     const bool tie = rr >= 0 && v == vmin;
     uint64_t m = c.g.ballot(tie);
     if (c.g.unib(popc(m) > 1)) {
@@ -1499,139 +1360,11 @@ template <typename T> DEV void foot_ll(V3<T> P1, V3<T> Q1, V3<T> P2, V3<T> Q2, V
 
 // case_04 (:575-669) on the set in sx/sy/sz[0..na) and the 2-point set (b0, b1):
 // SORT_CLOCK (:1513-1575) with a group-parallel angle argmin per step, then IS_INSIDE_PF of the
-// ordered polygon for b0 and b1 (group-parallel over edges).
+// ordered polygon for b0 and b1 (group-parallel over edges).  The point sets stay in LDS: each lane
+// reads its set elements (sx/sy/sz[i]), the ordered polygon (sx[ord[q]]) and its next vertex from the
+// group's LDS image at each use instead of holding K-element copies in registers, so the contact
+// kernel does not carry 60 VGPRs for the quarter of its pairs that take case_04.
 CTX_T DEV int contact_case04(CTX& c, int na, V3<T> b0, V3<T> b1, V3<T>& res) {
-    auto& C = c.L.u.c;
-    const int gl = c.g.gl;
-    const T TWO_PI_SP = (T)(2.0f * 3.14159274101257324f);
-    // OVERLAP (:1399-1418): all points pairwise within 1e-12 -> order unchanged
-    bool diff = false;
-    for (int i0 = 0; i0 < na; i0 += G) {
-        int i = i0 + gl;
-        if (i < na) {
-            const V3<T> pi = set_pt(c, i);
-            for (int j = 0; j < na; ++j) {
-                const V3<T> pj = set_pt(c, j);
-                diff = diff || fabs(pi.x - pj.x) > Tol<T>::Z || fabs(pi.y - pj.y) > Tol<T>::Z || fabs(pi.z - pj.z) > Tol<T>::Z;
-            }
-        }
-    }
-    const bool ovl = !c.g.any(diff);
-    T px[K], py[K], pz[K];
-    bool used[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        int i = k * G + gl;
-        const V3<T> q = set_pt(c, i < na ? i : 0);
-        px[k] = q.x; py[k] = q.y; pz[k] = q.z;
-        used[k] = false;
-    }
-    if (!ovl) {
-        T sx = 0, sy = 0, sz = 0;
-        for (int i = 0; i < na; ++i) { const V3<T> q = set_pt(c, i); sx += q.x; sy += q.y; sz += q.z; }
-        const T dn = (T)na;
-        const V3<T> cen = vmk<T>(sx / dn, sy / dn, sz / dn);
-        const V3<T> p0 = set_pt(c, 0);
-        const V3<T> nrm = cross(vsub(set_pt(c, 1), p0), vsub(set_pt(c, 2), p0));
-        V3<T> prev = p0;
-        if (gl == 0) C.ord[0] = 0u;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            int i = k * G + gl;
-            used[k] = i < na && px[k] == p0.x && py[k] == p0.y && pz[k] == p0.z;
-        }
-        for (int s = 1; s < na; ++s) {
-            T best = Tol<T>::BIG;
-            int bi = 0x7fffffff;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                int j = k * G + gl;
-                if (j < na && !used[k]) {
-                    V3<T> w1 = vsub(vmk<T>(px[k], py[k], pz[k]), cen), w2 = vsub(prev, cen);
-                    T ang = tatan2(dot(nrm, cross(w2, w1)), dot(w1, w2));
-                    ang = tfmod(ang + TWO_PI_SP, TWO_PI_SP);
-                    if (ang < best) { best = ang; bi = j; }
-                }
-            }
-            gargmin<G>(best, bi);
-            bi = c.g.uni(bi);
-            if (bi == 0x7fffffff) return GJKEPA_STATUS_DEGENERATE;
-            prev = set_pt(c, bi);
-            if (gl == 0) C.ord[s] = (uint32_t)bi;
-#pragma unroll
-            for (int k = 0; k < K; ++k) used[k] = used[k] || (px[k] == prev.x && py[k] == prev.y && pz[k] == prev.z);
-        }
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            int q = k * G + gl;
-            if (q < na) { const V3<T> p = set_pt(c, (int)C.ord[q]); px[k] = p.x; py[k] = p.y; pz[k] = p.z; }
-        }
-    }
-    // next polygon vertex of each lane's element, through the pol[] exchange
-    T nxv[K], nyv[K], nzv[K];
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < K; ++k) { int q = k * G + gl; if (q < na) C.pol[q] = px[k]; }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < K; ++k) { int q = k * G + gl; int j = (q == na - 1) ? 0 : q + 1; nxv[k] = q < na ? C.pol[j] : T(0); }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < K; ++k) { int q = k * G + gl; if (q < na) C.pol[q] = py[k]; }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < K; ++k) { int q = k * G + gl; int j = (q == na - 1) ? 0 : q + 1; nyv[k] = q < na ? C.pol[j] : T(0); }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < K; ++k) { int q = k * G + gl; if (q < na) C.pol[q] = pz[k]; }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < K; ++k) { int q = k * G + gl; int j = (q == na - 1) ? 0 : q + 1; nzv[k] = q < na ? C.pol[j] : T(0); }
-    __builtin_amdgcn_wave_barrier();
-    // IS_INSIDE_PF(sorted polygon, b_t) for t = 0, 1
-    int cnt_in = 0;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const V3<T> P = t ? b1 : b0;
-        T cp[K];
-        bool pos = false;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            int q = k * G + gl;
-            cp[k] = (nxv[k] - px[k]) * (P.y - py[k]) - (nyv[k] - py[k]) * (P.x - px[k]);
-            if (fabs(cp[k]) < Tol<T>::Z) cp[k] = T(0);
-            pos = pos || (q < na && cp[k] > Tol<T>::POS);
-        }
-        if (!c.g.any(pos)) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) cp[k] = (nxv[k] - px[k]) * (P.z - pz[k]) - (nzv[k] - pz[k]) * (P.x - px[k]);
-        }
-        if (gl == 0) C.pol[0] = cp[0];     // element 0 lives on group lane 0, slot 0
-        __builtin_amdgcn_wave_barrier();
-        const T c0 = C.pol[0];
-        __builtin_amdgcn_wave_barrier();
-        bool neg = false;
-#pragma unroll
-        for (int k = 0; k < K; ++k) { int q = k * G + gl; neg = neg || (q < na && c0 * cp[k] < T(0)); }
-        if (!c.g.any(neg)) ++cnt_in;
-    }
-    if (cnt_in == 0) {                                             // case_04_1
-        T sx = 0, sy = 0, sz = 0;
-        for (int i = 0; i < na; ++i) { const V3<T> q = set_pt(c, i); sx += q.x; sy += q.y; sz += q.z; }
-        const T dn = (T)na;
-        res = foot_pl(vmk<T>(sx / dn, sy / dn, sz / dn), b0, b1);
-    } else {
-        res = vscl(T(0.5), vadd(b0, b1));                          // case_04_2 / case_04_3
-    }
-    return 0;
-}
-
-// case_04 with the point sets left in LDS (GJKEPA_CASE04_LDS): the same arithmetic as contact_case04,
-// but each lane reads its set elements (sx/sy/sz[i]), the ordered polygon (sx[ord[q]]) and its next
-// vertex from the group's LDS image at each use instead of holding K-element copies in registers, so
-// the contact kernel does not carry 60 VGPRs for the quarter of its pairs that take case_04.
-CTX_T DEV int contact_case04_lds(CTX& c, int na, V3<T> b0, V3<T> b1, V3<T>& res) {
     auto& C = c.L.u.c;
     const int gl = c.g.gl;
     const T TWO_PI_SP = (T)(2.0f * 3.14159274101257324f);
@@ -1735,9 +1468,6 @@ CTX_T DEV int contact_case04_lds(CTX& c, int na, V3<T> b0, V3<T> b1, V3<T>& res)
     }
     return 0;
 }
-#ifndef GJKEPA_CASE04_LDS
-#define GJKEPA_CASE04_LDS 1      // case_04 reads its point sets from LDS (0: register copies, A/B)
-#endif
 
 // get_collisionPoint_02 (:457-696)
 CTX_T DEV int contact_v2(CTX& c, const DotSet<T, K>& D, V3<T>& res) {
@@ -1771,13 +1501,13 @@ CTX_T DEV int contact_v2(CTX& c, const DotSet<T, K>& D, V3<T>& res) {
         const V3<T> q0 = set_pt(c, 0), q1 = set_pt(c, 1);
         __builtin_amdgcn_wave_barrier();
         band_set(c, 1, D, t2, true);
-        return GJKEPA_CASE04_LDS ? contact_case04_lds(c, n2, q0, q1, res) : contact_case04(c, n2, q0, q1, res);
+        return contact_case04(c, n2, q0, q1, res);
     } else if (n1 >= 3 && n2 == 2) {                               // case_04(SPT_p1, SPT_p2)
         band_set(c, 1, D, t2, true);
         const V3<T> q0 = set_pt(c, 0), q1 = set_pt(c, 1);
         __builtin_amdgcn_wave_barrier();
         band_set(c, 0, D, t1, true);
-        return GJKEPA_CASE04_LDS ? contact_case04_lds(c, n1, q0, q1, res) : contact_case04(c, n1, q0, q1, res);
+        return contact_case04(c, n1, q0, q1, res);
     } else if (n1 >= 3 && n2 >= 3) {                               // case_05
         band_set(c, 0, D, t1, true);
         T sx = 0, sy = 0, sz = 0;
@@ -1904,12 +1634,11 @@ CTX_T DEV bool warm_start(CTX& c, const uint32_t* w, uint32_t* kc) {
 // Sphere pre-test + GJK.  Returns PH_MISS, PH_HIT (codes k0..k3 filled) or an error status.  With `so`
 // (seed hand-over), a hit also returns this quad lane's face normal of the final simplex and whether
 // EPA may seed from the quad's normals.
-CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, bool try_axis = false, SeedOut<T>* so = nullptr) {
+CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, SeedOut<T>* so = nullptr) {
     const V3<T> O = zero3<T>();
     auto& L = c.L;
     const int gl = c.g.gl;
     gjk_it = 0;
-    bool axis_sep = false;
     {   // RoughCollisionDetection_SphericalEnvelope (:1165-1188)
         // the six sequential coordinate sums run on group lanes (sum j on lane j % G: hull j/3, axis j%3)
         T cs[(6 + G - 1) / G];           // centroid coordinate j0 + gl of pass j0 / G (hull j / 3, axis j % 3)
@@ -1919,24 +1648,18 @@ CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, bool try_axis = false
             cs[j0 / G] = T(0);
             if (j < 6) {
                 const int h = j / 3, ax = j - 3 * (j / 3);
-#if GJKEPA_HULL_AOS
-                const TH* col = &L.hv[h][0].x + ax;  // coordinate ax of vertex i at col[4 i]
-                constexpr int CS = 4;
-#else
                 const TH* col = ax == 0 ? L.hx[h] : ax == 1 ? L.hy[h] : L.hz[h];
-                constexpr int CS = 1;
-#endif
                 const int n = h ? c.nb : c.na;
                 T sum = 0;
                 int i = 0;
                 for (; i + 8 <= n; i += 8) {         // loads batched ahead of the in-order adds
                     TH v[8];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] = col[CS * (i + u)];
+                    for (int u = 0; u < 8; ++u) v[u] = col[i + u];
 #pragma unroll
                     for (int u = 0; u < 8; ++u) sum += (T)v[u];
                 }
-                for (; i < n; ++i) sum += (T)col[CS * i];
+                for (; i < n; ++i) sum += (T)col[i];
                 cs[j0 / G] = sum / (T)n;
             }
         }
@@ -1960,28 +1683,6 @@ CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, bool try_axis = false
         r2 = tsqrt(gmax<G>(r2));
         GK_STAMP(SG_SPHERE);
         if (!c.g.unib(norm2(vsub(m1, m2)) <= r1 + r2 + T(1))) return PH_MISS;
-        // Diagnostic quick reject (GJKEPA_AXIS_REJECT builds only): the axis between the hull
-        // centres separates the hulls by more than kWarmMargin, so a pair the initial-simplex block
-        // does not call a hit is answered "miss" without the tetrahedron loop.  NOT parity-safe:
-        // the reference's loop can still report a hit on such a pair through isPointInSimplex's
-        // on-face branch (:1246-1256), e.g. a unit cube vs the cube moved by (-1, 0, 2).
-        if (try_axis) {
-            const V3<T> d = vsub(m2, m1);
-            T amax = -Tol<T>::BIG, bmin = Tol<T>::BIG;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const int i = k * G + gl;
-                const V3<T> pa = c.AV(k), pb = c.BV(k);
-                const T ta = d.x * pa.x + d.y * pa.y + d.z * pa.z;
-                const T tb = d.x * pb.x + d.y * pb.y + d.z * pb.z;
-                if (i < c.na && ta > amax) amax = ta;
-                if (i < c.nb && tb < bmin) bmin = tb;
-            }
-            amax = gmax<G>(amax);
-            bmin = gmin<G>(bmin);
-            const T margin = sizeof(T) == 8 ? T(kWarmMargin) : T(1e-4);
-            axis_sep = c.g.unib(bmin - amax > margin * norm2(d));
-        }
     }
     // --- initial simplex (:82-170)
     V3<T> s0 = O, s1 = O, s2 = O, s3 = O;   // fresh SAVE state: stale row 4 = 0
@@ -2016,9 +1717,6 @@ CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, bool try_axis = false
         if (c.g.unib(quad_inside(q, s0, s1, s2, s3, nq))) enter = true;
     }
     GK_STAMP(SG_INIT);
-    // the quick reject answers only after the initial-simplex block: that block is where the
-    // reference reports hits for separated tie-heavy hulls (origin on the initial triangle's plane)
-    if (!enter && axis_sep) return PH_MISS;
     if (!enter) {
         // cycle history (:193-194): coordinate j < 12 of last1 / last2 lives on group lane j % G,
         // slot j / G
@@ -2141,10 +1839,11 @@ CTX_T DEV bool load_hulls(CTX& c, const TH* __restrict__ pa, const TH* __restric
     for (int k = 0; k < K; ++k) {
         const int i = k * G + gl;
         TH ax = 0, ay = 0, az = 0, bx = 0, by = 0, bz = 0;
-        // slots past the count: zeros, or vertex 0 again (GJKEPA_PAD_V0, support_dots)
+        // slots past the count: vertex 0 again, so the support scans need no mask (support_dots);
+        // nothing is read from an empty hull (`i < n ||` is implied, and keeps the generated code as it was)
         const int ja = i < c.na ? i : 0, jb = i < c.nb ? i : 0;
-        if (i < c.na || (GJKEPA_PAD_V0 && c.na > 0)) { ax = pa[ja]; ay = pa[c.na + ja]; az = pa[2 * c.na + ja]; }
-        if (i < c.nb || (GJKEPA_PAD_V0 && c.nb > 0)) { bx = pb[jb]; by = pb[c.nb + jb]; bz = pb[2 * c.nb + jb]; }
+        if (i < c.na || c.na > 0) { ax = pa[ja]; ay = pa[c.na + ja]; az = pa[2 * c.na + ja]; }
+        if (i < c.nb || c.nb > 0) { bx = pb[jb]; by = pb[c.nb + jb]; bz = pb[2 * c.nb + jb]; }
         nonfinite = nonfinite || !isfinite(ax) || !isfinite(ay) || !isfinite(az) || !isfinite(bx) ||
                     !isfinite(by) || !isfinite(bz);
         if constexpr (kScreen) {
@@ -2155,13 +1854,8 @@ CTX_T DEV bool load_hulls(CTX& c, const TH* __restrict__ pa, const TH* __restric
             c.ax[k] = (T)ax; c.ay[k] = (T)ay; c.az[k] = (T)az;
             c.bx[k] = (T)bx; c.by[k] = (T)by; c.bz[k] = (T)bz;
         }
-#if GJKEPA_HULL_AOS
-        c.L.hv[0][i] = HV<TH>{ax, ay, az, TH(0)};
-        c.L.hv[1][i] = HV<TH>{bx, by, bz, TH(0)};
-#else
         c.L.hx[0][i] = ax; c.L.hy[0][i] = ay; c.L.hz[0][i] = az;
         c.L.hx[1][i] = bx; c.L.hy[1][i] = by; c.L.hz[1][i] = bz;
-#endif
     }
     if constexpr (kScreen) {
         c.vmax_a = gmax<G>(ma);
@@ -2441,7 +2135,7 @@ __global__ __launch_bounds__(64, MINW) void gjk_kernel(const gjkepa_gjk_args a) 
                 }
                 SeedOut<T> so{zero3<T>(), false};     // a warm-start hit hands nothing over
                 if (warm_hit) r = PH_HIT;
-                else r = gjk_phase(c, kc, gjk_it, GJKEPA_AXIS_REJECT != 0, &so);
+                else r = gjk_phase(c, kc, gjk_it, &so);
                 __builtin_amdgcn_wave_barrier();
                 GK_STAMP(SG_CHK);
                 if (WARM && gl < 4)     // this call's simplex seeds the next call; a miss mark; none for errors
@@ -2479,15 +2173,8 @@ __global__ __launch_bounds__(64, MINW) void gjk_kernel(const gjkepa_gjk_args a) 
         __builtin_amdgcn_wave_barrier();
         GK_STAMP(SG_STORE);
     };
-#if GJKEPA_GJK_META
     for_each_routed_pair<G, true>(grp, a.n_pairs, a.route, a.route_code, a.ctr, claim, false, body, a.pairs, a.hull_cnt,
                                   a.hull_off);
-#else
-    for_each_routed_pair<G>(grp, a.n_pairs, a.route, a.route_code, a.ctr, claim, false, [&](int64_t pair) {
-        const int32_t ha = a.pairs[2 * pair], hb = a.pairs[2 * pair + 1];
-        body(pair, PairMeta{a.hull_cnt[ha], a.hull_cnt[hb], a.hull_off[ha], a.hull_off[hb]});
-    });
-#endif
     GK_STAMP(SG_ROUTE);
     tally_end(a.tally);
     GK_STAMP_END();
@@ -2697,11 +2384,10 @@ __global__ __launch_bounds__(64, MINW) void epa_kernel_refill(const gjkepa_epa_a
             if (c.na <= G * K && c.nb <= G * K) {
                 const V3<T> s0 = decode_pt(c, kc[0]), s1 = decode_pt(c, kc[1]), s2 = decode_pt(c, kc[2]), s3 = decode_pt(c, kc[3]);
                 if (gl == 0) tally_route(seed.on ? GJKEPA_TALLY_SEED_HANDED : GJKEPA_TALLY_SEED_OWN);
-#if GJKEPA_EPA_SEED
+                // a fresh pair's iteration 1 joins the common support step
                 r = epa_seed(c, S, s0, s1, s2, s3, seed);
                 seeded = r == 0;
                 if (r == ST_FALLBACK)
-#endif
                     r = epa_begin(c, S, s0, s1, s2, s3, seed);
             }
             __builtin_amdgcn_wave_barrier();
@@ -2769,7 +2455,7 @@ DEV bool query_pair_k(unsigned char* smem, const Grp<64>& grp, const TIn* pa, co
     }
     uint32_t kc[4];
     int gjk_it = 0;
-    int r = gjk_phase(c, kc, gjk_it, GJKEPA_AXIS_REJECT != 0);
+    int r = gjk_phase(c, kc, gjk_it);
     __builtin_amdgcn_wave_barrier();
     if (r == PH_MISS) {
         store_record<64, RT>(out, pair, gl, o, 0, 0, 0, 0u);
@@ -2997,15 +2683,8 @@ __global__ __launch_bounds__(64, MINW) void contact_kernel(const gjkepa_epa_args
         __builtin_amdgcn_wave_barrier();
         GK_STAMP(SC_STORE);
     };
-#if GJKEPA_CONTACT_META
     for_each_routed_pair<G, true>(grp, a.n_pairs, a.route, a.route_code, a.ctr, claim, a.grid == GJKEPA_GRID_UNITS, body,
                                   a.pairs, a.hull_cnt, a.hull_off);
-#else
-    for_each_routed_pair<G>(grp, a.n_pairs, a.route, a.route_code, a.ctr, claim, a.grid == GJKEPA_GRID_UNITS, [&](int64_t pair) {
-        const int32_t ha = a.pairs[2 * pair], hb = a.pairs[2 * pair + 1];
-        body(pair, PairMeta{a.hull_cnt[ha], a.hull_cnt[hb], a.hull_off[ha], a.hull_off[hb]});
-    });
-#endif
     GK_STAMP(SC_ROUTE);
     tally_end(a.tally);
     GK_STAMP_END();
@@ -3134,13 +2813,13 @@ GK_EPA_DEF(0, EPA_ARGS(0), GJKEPA_E0_REFILL)
 GK_EPA_DEF(1, EPA_ARGS(1), GJKEPA_E1_REFILL)
 #endif
 #if GK_IN(6)
-GK_EPA_DEF(2, EPA_ARGS(2), GJKEPA_E2_REFILL, GJKEPA_PARK ? 1 : 0)     // parks
+GK_EPA_DEF(2, EPA_ARGS(2), GJKEPA_E2_REFILL, 1)     // parks
 #endif
 #if GK_IN(7)
-GK_EPA_DEF(3, EPA_ARGS(3), 0, GJKEPA_PARK ? 1 : 0)                    // parks
+GK_EPA_DEF(3, EPA_ARGS(3), 0, 1)                    // parks
 #endif
 #if GK_IN(8)
-GK_EPA_DEF(4, EPA_ARGS(4), 0, GJKEPA_PARK ? 2 : 0)                    // resumes
+GK_EPA_DEF(4, EPA_ARGS(4), 0, 2)                    // resumes
 #endif
 #if GK_IN(9)
 GK_EPA_DEF(5, EPA_ARGS(5))

@@ -9,10 +9,6 @@
 #include <cmath>
 #include <cstdint>
 
-#ifndef GJKEPA_FMAX_REDUCE
-#define GJKEPA_FMAX_REDUCE 1
-#endif
-
 namespace gk {
 
 #define DEV __device__ __forceinline__
@@ -172,13 +168,13 @@ template <int S, int N, typename T> DEV void argmin_steps(T& v, int& i) {
 // Value-only max / min reductions.  Floating values take v_max_f64 / v_min_f64 (one instruction a
 // step instead of compare + two selects): the callers only compare against the result or use values
 // that cannot be -0 (squared norms, |distances|), and a NaN operand never wins — as in the
-// reference's sequential `IF (t > mx)` scans.  (GJKEPA_FMAX_REDUCE=0: the select form, for A/B.)
+// reference's sequential `IF (t > mx)` scans.
 template <typename T> DEV T red_max(T a, T b) {
-    if constexpr (GJKEPA_FMAX_REDUCE && (sizeof(T) == 8 || sizeof(T) == 4) && T(0.5) != T(0)) return __builtin_fmax(a, b);
+    if constexpr ((sizeof(T) == 8 || sizeof(T) == 4) && T(0.5) != T(0)) return __builtin_fmax(a, b);
     else return a > b ? a : b;
 }
 template <typename T> DEV T red_min(T a, T b) {
-    if constexpr (GJKEPA_FMAX_REDUCE && (sizeof(T) == 8 || sizeof(T) == 4) && T(0.5) != T(0)) return __builtin_fmin(a, b);
+    if constexpr ((sizeof(T) == 8 || sizeof(T) == 4) && T(0.5) != T(0)) return __builtin_fmin(a, b);
     else return a < b ? a : b;
 }
 template <int S, int N, typename T> DEV void max_steps(T& v) {
