@@ -6,7 +6,9 @@
 // allocates or synchronises: it enqueues a 256-byte counter / tally reset and the tier kernels (2 GJK +
 // 5 EPA tiers, and the contact passes, forked onto a second stream for large batches); each kernel
 // takes 64-pair chunks (or runs of 16) from its own counter.  gjkepa_hull_batch(_device) follow the
-// same pattern for the batched convex-hull kernels (two tiers over one cloud list).
+// same pattern for the batched convex-hull kernels (two tiers over one cloud list), and
+// gjkepa_distance_batch(_device) for the separation-distance tiers (a counter reset and three launches on
+// the caller's stream, counters in a workspace of their own).
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -100,6 +102,7 @@ struct DeviceState {
     DevBuf b_pairs, b_count, b_ws;                          // gjkepa_broadphase staging
     DevBuf c_idx, c_hits, c_ws, c_n;                        // gjkepa_collide staging
     DevBuf q_blk, q_ws;                                     // combined gjkepa_query batches
+    DevBuf d_rec, d_out, d_ws;                              // gjkepa_distance_batch staging
     HostBuf q_host;
 };
 
@@ -826,6 +829,128 @@ int gjkepa_batch(int32_t version, double tol_ff, int32_t vert_dtype, int32_t pre
                  (int64_t)d->ws.cap, s, d->num_cus);
     if (rc) return rc;
     if ((e = hipMemcpyAsync(out, d->out.p, (size_t)n_pairs * rec, hipMemcpyDeviceToHost, s)) != hipSuccess)
+        return hip_fail(e, "hipMemcpyAsync D2H");
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    return 0;
+}
+
+// ---- separation distance -------------------------------------------------------------------------
+int gjkepa_distance_record_bytes(void) { return (int)sizeof(gjkepa_distance_f64); }
+
+int64_t gjkepa_distance_workspace_bytes(int64_t n_pairs) {
+    if (n_pairs < 0) return GJKEPA_E_ARG;
+    return GJKEPA_DIST_WS_BYTES;       // the tier launches' chunk counters: independent of the batch size
+}
+
+}  // extern "C"
+
+namespace {
+static_assert(sizeof(gjkepa_distance_f64) == 128, "gjkepa_distance_f64 layout (gjkepa.py DIST64)");
+static_assert(GJKEPA_GJK_TIERS * sizeof(uint32_t) <= GJKEPA_DIST_WS_BYTES, "one counter per distance tier");
+// the checks the device and the host entry share, before any device work
+int distance_args_ok(int32_t vert_dtype, int64_t n_pairs, const void* records, int32_t records_precision,
+                     double max_distance) {
+    if (n_pairs < 0 || (vert_dtype != GJKEPA_DTYPE_F32 && vert_dtype != GJKEPA_DTYPE_F64))
+        return fail(GJKEPA_E_ARG, "bad n_pairs/dtype");
+    if (records && records_precision != GJKEPA_PREC_F32 && records_precision != GJKEPA_PREC_F64)
+        return fail(GJKEPA_E_ARG, "bad records_precision");
+    if (!(max_distance >= 0.0)) return fail(GJKEPA_E_ARG, "max_distance is NaN or negative");
+    if (n_pairs > INT32_MAX) return fail(GJKEPA_E_ARG, "n_pairs above 2^31-1");
+    return 0;
+}
+// the chain: counter reset, then one launch per tier, all on the caller's stream
+int distance_enqueue(int32_t vert_dtype, const void* verts, const int64_t* hull_off, const int32_t* hull_cnt,
+                     const int32_t* pairs, int64_t n_pairs, const void* records, int32_t records_precision,
+                     double max_distance, void* out, void* workspace, int64_t ws_bytes, hipStream_t s, int num_cus) {
+    if (n_pairs == 0) return 0;
+    if (ws_bytes < GJKEPA_DIST_WS_BYTES) return fail(GJKEPA_E_WORKSPACE, "workspace too small");
+    uint32_t* ctr = (uint32_t*)workspace;
+    hipError_t e;
+    if ((e = gjkepa_launch_ws_reset(ctr, GJKEPA_DIST_WS_BYTES / 4, s)) != hipSuccess)
+        return hip_fail(e, "distance workspace reset");
+    gjkepa_dist_args a{};
+    a.verts = verts;
+    a.hull_off = hull_off;
+    a.hull_cnt = hull_cnt;
+    a.pairs = pairs;
+    a.n_pairs = n_pairs;
+    a.records = (const unsigned char*)records;
+    a.rec_stride = records_precision == GJKEPA_PREC_F64 ? (int)sizeof(gjkepa_contact_f64) : (int)sizeof(gjkepa_contact_f32);
+    a.rec_hit_off = records_precision == GJKEPA_PREC_F64 ? (int)offsetof(gjkepa_contact_f64, collision)
+                                                         : (int)offsetof(gjkepa_contact_f32, collision);
+    a.max_distance = max_distance;
+    a.out = out;
+    a.num_cus = num_cus;
+    for (int t = 0; t < GJKEPA_GJK_TIERS; ++t) {
+        a.ctr = ctr + t;
+        if ((e = gjkepa_launch_dist(t, vert_dtype, a, s)) != hipSuccess) return hip_fail(e, "distance tier launch");
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int gjkepa_distance_batch_device(int32_t vert_dtype, const void* verts, const int64_t* hull_off,
+                                 const int32_t* hull_cnt, const int32_t* pairs, int64_t n_pairs,
+                                 const void* records, int32_t records_precision, double max_distance,
+                                 void* out, void* workspace, int64_t workspace_bytes, void* stream) {
+    const gjkepa_internal::Range range_("gjkepa_distance_batch_device (chain enqueue)");
+    int rc = distance_args_ok(vert_dtype, n_pairs, records, records_precision, max_distance);
+    if (rc) return rc;
+    if (n_pairs > 0 && (!verts || !hull_off || !hull_cnt || !pairs || !out || !workspace))
+        return fail(GJKEPA_E_ARG, "null pointer");
+    if (n_pairs == 0) return 0;
+    if (workspace_bytes < GJKEPA_DIST_WS_BYTES) return fail(GJKEPA_E_WORKSPACE, "workspace too small");
+    return distance_enqueue(vert_dtype, verts, hull_off, hull_cnt, pairs, n_pairs, records, records_precision,
+                            max_distance, out, workspace, workspace_bytes, (hipStream_t)stream, num_cus_current());
+}
+
+int gjkepa_distance_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
+                          const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                          const int32_t* pairs, int64_t n_pairs, const void* records,
+                          int32_t records_precision, double max_distance, void* out, int32_t device) {
+    const gjkepa_internal::Range range_("gjkepa_distance_batch (H2D, chain, D2H)");
+    if (n_hulls < 0 || n_vert_scalars < 0) return fail(GJKEPA_E_ARG, "bad sizes");
+    int rc = distance_args_ok(vert_dtype, n_pairs, records, records_precision, max_distance);
+    if (rc) return rc;
+    if (n_pairs == 0) return 0;
+    if (!verts || !hull_off || !hull_cnt || !pairs || !out) return fail(GJKEPA_E_ARG, "null pointer");
+    // host-side validation of the index structure (device code trusts it), as gjkepa_batch
+    for (int64_t k = 0; k < 2 * n_pairs; ++k)
+        if (pairs[k] < 0 || pairs[k] >= n_hulls) return fail(GJKEPA_E_ARG, "pair references a missing hull");
+    for (int64_t h = 0; h < n_hulls; ++h) {
+        int64_t c = hull_cnt[h];
+        if (c >= 1 && (hull_off[h] < 0 || hull_off[h] + 3 * c > n_vert_scalars))
+            return fail(GJKEPA_E_ARG, "hull outside the vertex pool");
+    }
+    DeviceState* d = device_state(device, &rc);
+    if (!d) return rc;
+    std::lock_guard<std::mutex> g(d->mu);
+    if ((rc = init_device(d, device))) return rc;
+    hipError_t e;
+    const size_t esz = vert_dtype == GJKEPA_DTYPE_F32 ? 4 : 8;
+    const size_t rec = records ? (size_t)gjkepa_record_bytes(records_precision) : 0;
+    if ((e = d->verts.ensure((size_t)n_vert_scalars * esz)) != hipSuccess ||
+        (e = d->off.ensure((size_t)n_hulls * 8)) != hipSuccess ||
+        (e = d->cnt.ensure((size_t)n_hulls * 4)) != hipSuccess ||
+        (e = d->pairs.ensure((size_t)n_pairs * 8)) != hipSuccess ||
+        (e = d->d_rec.ensure((size_t)n_pairs * rec)) != hipSuccess ||
+        (e = d->d_out.ensure((size_t)n_pairs * sizeof(gjkepa_distance_f64))) != hipSuccess ||
+        (e = d->d_ws.ensure((size_t)GJKEPA_DIST_WS_BYTES)) != hipSuccess)
+        return hip_fail(e, "hipMalloc");
+    hipStream_t s = d->stream;
+    if ((e = hipMemcpyAsync(d->verts.p, verts, (size_t)n_vert_scalars * esz, hipMemcpyHostToDevice, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(d->off.p, hull_off, (size_t)n_hulls * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(d->cnt.p, hull_cnt, (size_t)n_hulls * 4, hipMemcpyHostToDevice, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(d->pairs.p, pairs, (size_t)n_pairs * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
+        (records && (e = hipMemcpyAsync(d->d_rec.p, records, (size_t)n_pairs * rec, hipMemcpyHostToDevice, s)) != hipSuccess))
+        return hip_fail(e, "hipMemcpyAsync H2D");
+    rc = distance_enqueue(vert_dtype, d->verts.p, (const int64_t*)d->off.p, (const int32_t*)d->cnt.p,
+                          (const int32_t*)d->pairs.p, n_pairs, records ? d->d_rec.p : nullptr, records_precision,
+                          max_distance, d->d_out.p, d->d_ws.p, (int64_t)d->d_ws.cap, s, d->num_cus);
+    if (rc) return rc;
+    if ((e = hipMemcpyAsync(out, d->d_out.p, (size_t)n_pairs * sizeof(gjkepa_distance_f64), hipMemcpyDeviceToHost, s)) != hipSuccess)
         return hip_fail(e, "hipMemcpyAsync D2H");
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     return 0;

@@ -354,6 +354,37 @@ __host__ __device__ inline uint32_t gjkepa_guard_of(const gjkepa_epa_args& a) {
     return gjkepa_fold(h);
 }
 
+// ---- separation distance (gjkepa_distance_batch_device): a distance GJK in fp64, one launch per GJK
+// tier shape (GJKEPA_G0/G1/G2_{G,K}).  Every launch scans the whole pair list and takes the pairs whose
+// larger hull falls in its bracket (1-32 / 33-128 / 129-256 vertices; tier 0 also answers bad counts),
+// decided from the hull counts: no route bytes, and chunk counters of the entry's own workspace.
+#ifndef GJKEPA_D0_MINW
+#define GJKEPA_D0_MINW 2        // waves per SIMD of the distance tiers (the simplex: four points, weights, codes)
+#endif
+#ifndef GJKEPA_D1_MINW
+#define GJKEPA_D1_MINW 2
+#endif
+#ifndef GJKEPA_D2_MINW
+#define GJKEPA_D2_MINW 2
+#endif
+#define GJKEPA_DIST_WS_BYTES 256    // workspace: one uint32 chunk counter per tier launch (64 words kept)
+struct gjkepa_dist_args {
+    const void* verts;
+    const int64_t* hull_off;
+    const int32_t* hull_cnt;
+    const int32_t* pairs;
+    int64_t n_pairs;
+    const unsigned char* records;   // optional contact records of the same pair list (nullptr: none)
+    int rec_stride;                 // bytes per contact record, and the offset of its collision byte
+    int rec_hit_off;
+    double max_distance;            // early-out bound (+inf: none)
+    uint32_t* ctr;                  // this launch's chunk counter (zero at launch)
+    void* out;                      // gjkepa_distance_f64 records
+    int grid;                       // <= 0: occupancy x CUs
+    int num_cus;
+};
+hipError_t gjkepa_launch_dist(int tier, int vert_dtype, const gjkepa_dist_args& a, hipStream_t s);
+
 hipError_t gjkepa_launch_gjk(int tier, int vert_dtype, int precision, const gjkepa_gjk_args& a, hipStream_t s);
 hipError_t gjkepa_launch_epa(int tier, int vert_dtype, int precision, const gjkepa_epa_args& a, hipStream_t s);
 // contact tiers take the same argument block (route_code = GJKEPA_ROUTE_CT0 + tier; next_code unused)

@@ -38,6 +38,9 @@
 #else
 #define GK_IN(p) 1
 #endif
+#if GK_IN(12)
+#include "dist_simplex.h"       // the distance GJK's simplex arithmetic (host and device)
+#endif
 
 namespace gk {
 
@@ -2702,13 +2705,150 @@ __global__ __launch_bounds__(64) void ws_reset_kernel(uint32_t* ws, int n32, uin
 }
 #endif  // GK_IN(0)
 
+#if GK_IN(12)
+// ---------------------------------------------------------------- separation distance
+// gjkepa_distance_f64: 13 doubles (distance, point_a, point_b, normal, lambda), code[3], the four
+// int8 fields, iters, pad.  Its 16 8-byte words are stored from registers, word j by group lane j % G.
+template <int G> DEV void store_dist(void* out, int64_t pair, int gl, const double* o13, const uint32_t* code, int n,
+                                     int status, int flags, uint32_t iters) {
+    const uint32_t tail = (uint32_t)(n & 0xff) | ((uint32_t)(status & 0xff) << 8) | ((uint32_t)(flags & 0xff) << 16);
+#pragma unroll
+    for (int j0 = 0; j0 < 16; j0 += G) {
+        const int j = j0 + gl;
+        if (j >= 16) break;
+        double v = 0.0;
+#pragma unroll
+        for (int i = 0; i < 13; ++i) v = (j == i) ? o13[i] : v;
+        uint64_t word = __builtin_bit_cast(uint64_t, v);
+        if (j == 13) word = (uint64_t)code[0] | ((uint64_t)code[1] << 32);
+        if (j == 14) word = (uint64_t)code[2] | ((uint64_t)tail << 32);
+        if (j == 15) word = (uint64_t)iters;
+        reinterpret_cast<uint64_t*>(out)[pair * 16 + j] = word;
+    }
+}
+
+// a record with nothing computed (bad input, or skipped as a hit), written whole by one lane
+DEV void store_dist_empty(void* out, int64_t pair, int status, int flags) {
+    uint64_t* w = reinterpret_cast<uint64_t*>(out) + pair * 16;
+#pragma unroll
+    for (int j = 0; j < 13; ++j) w[j] = 0ull;
+    w[13] = ~0ull;
+    w[14] = (uint64_t)gkd::kDistNoCode | ((uint64_t)(((uint32_t)(status & 0xff) << 8) | ((uint32_t)(flags & 0xff) << 16)) << 32);
+    w[15] = 0ull;
+}
+
+// The distance tiers' work distribution: for_each_routed_pair's dense schedule (64-pair chunks and a
+// tail of small units from the launch's counter, Units / tail_unit / groups_take), with the pairs of
+// a unit chosen lane-parallel from the hull counts and the contact records instead of a route byte:
+// lane l looks at pair p0 + l, answers it itself when nothing is to be computed (a bad count in tier 0;
+// a hit of this tier's bracket), and only the pairs left go to the groups.  After a batch most
+// candidate pairs are hits (C2: 73%): handed to the groups they would leave three groups in four of
+// every round idle (measured, 2^20 C2 pairs: 1.99 ms with every pair handed out, 1.40 ms with this
+// filter; 2^22 C4 pairs 16.1 -> 10.5 ms).
+template <int G, int CAP, int TIER, typename F>
+DEV void for_each_dist_pair(const Grp<G>& grp, const gjkepa_dist_args& a, F&& f) {
+    constexpr int LO = TIER == 0 ? 0 : TIER == 1 ? GJKEPA_G0_G * GJKEPA_G0_K : GJKEPA_G1_G * GJKEPA_G1_K;
+    static_assert(LO < CAP, "tier brackets ascend");
+    const Units U(a.n_pairs, tail_unit<G, (64 / G > 8 ? 64 / G : 8)>(a.n_pairs));
+    uint32_t next = 0;
+    if ((int64_t)blockIdx.x < U.nunits && grp.lane == 0) next = gridDim.x + atomicAdd(a.ctr, 1u);
+    int64_t u = blockIdx.x;
+    while (u < U.nunits) {
+        if (grp.lane == 0 && u != (int64_t)blockIdx.x) next = gridDim.x + atomicAdd(a.ctr, 1u);   // prefetch
+        int64_t p0;
+        int len;
+        U.range(u, p0, len);
+        bool take = false;
+        if (grp.lane < len) {
+            const int64_t p = p0 + grp.lane;
+            const int na = a.hull_cnt[a.pairs[2 * p]], nb = a.hull_cnt[a.pairs[2 * p + 1]];
+            const int nmax = na > nb ? na : nb;
+            if (na < 1 || nb < 1 || na > GJKEPA_MAX_HULL_VERTS || nb > GJKEPA_MAX_HULL_VERTS) {
+                if (TIER == 0) store_dist_empty(a.out, p, GJKEPA_STATUS_BAD_INPUT, 0);
+            } else if (nmax > LO && nmax <= CAP) {
+                if (a.records && a.records[p * (int64_t)a.rec_stride + a.rec_hit_off] != 0)
+                    store_dist_empty(a.out, p, GJKEPA_STATUS_OK, GJKEPA_DIST_HIT);
+                else
+                    take = true;
+            }
+        }
+        groups_take<G, true>(grp, p0, __ballot(take), a.pairs, a.hull_cnt, a.hull_off, f);
+        u = (int64_t)__builtin_amdgcn_readfirstlane(next);
+    }
+}
+
+// Distance kernel of tier TIER (group shape G x K as GJK tier TIER): every pair of the list whose
+// larger hull has LO < n <= G K vertices (tier 0 also answers the bad counts).  The simplex logic
+// (dist_simplex.h) is group-uniform like gjk_phase's; the support scans are the contact path's.
+template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
+__global__ __launch_bounds__(64, MINW) void dist_kernel(const gjkepa_dist_args a) {
+    using T = double;
+    using L_t = Lds<T, TIn, G, K, 0, 0>;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const Grp<G> grp;
+    L_t& L = *reinterpret_cast<L_t*>(smem + lds_stride<L_t, G>() * (grp.lane / G));
+    const int gl = grp.gl;
+    const TIn* verts = (const TIn*)a.verts;
+    auto body = [&](int64_t pair, const PairMeta& pm) {      // a pair of this tier with valid counts, not skipped
+        Ctx<T, TIn, G, K, 0, 0, LH> c{L, grp};
+        const int na = grp.uni(pm.na), nb = grp.uni(pm.nb);
+        double o13[13];
+#pragma unroll
+        for (int i = 0; i < 13; ++i) o13[i] = 0.0;
+        uint32_t code[3] = {gkd::kDistNoCode, gkd::kDistNoCode, gkd::kDistNoCode};
+        c.na = na;
+        c.nb = nb;
+        if (load_hulls(c, verts + pm.oa, verts + pm.ob)) {
+            store_dist<G>(a.out, pair, gl, o13, code, 0, GJKEPA_STATUS_BAD_INPUT, 0, 0u);
+            __builtin_amdgcn_wave_barrier();
+            return;
+        }
+        gkd::Simplex s;
+        const gkd::Result r = gkd::dist_gjk(
+            s, a.max_distance,
+            [&](gkd::D3 d, int& ia, int& ib) { support_idx(c, vmk<T>(d.x, d.y, d.z), ia, ib); },
+            [&](int ia, int ib) { const V3<T> p = vsub(c.A(ia), c.B(ib)); return gkd::mk(p.x, p.y, p.z); },
+            [](double x) { return tsqrt(x); });
+        int n = 0, status = GJKEPA_STATUS_OK, flags = 0;
+        if (r.outcome == gkd::DIST_OVERLAP) {
+            flags = GJKEPA_DIST_OVERLAP;
+        } else {
+            // witness points from the weights and codes, term by term in simplex order
+            V3<T> pa = zero3<T>(), pb = zero3<T>();
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (k < s.n) {
+                    const V3<T> ak = c.A((int)(s.code[k] & 0xffffu)), bk = c.B((int)(s.code[k] >> 16));
+                    pa = vadd(pa, vscl(s.lam[k], ak));
+                    pb = vadd(pb, vscl(s.lam[k], bk));
+                    o13[10 + k] = s.lam[k];
+                    code[k] = s.code[k];
+                }
+            n = s.n;
+            const V3<T> d = vsub(pa, pb);
+            const T dist = norm2(d);
+            o13[0] = dist;
+            o13[1] = pa.x; o13[2] = pa.y; o13[3] = pa.z;
+            o13[4] = pb.x; o13[5] = pb.y; o13[6] = pb.z;
+            if (dist > T(0)) { o13[7] = d.x / dist; o13[8] = d.y / dist; o13[9] = d.z / dist; }
+            if (r.outcome == gkd::DIST_FAR) { flags = GJKEPA_DIST_FAR; o13[0] = r.lower; }
+            if (r.outcome == gkd::DIST_MAXITER) status = GJKEPA_STATUS_DIST_MAXITER;
+        }
+        __builtin_amdgcn_wave_barrier();
+        store_dist<G>(a.out, pair, gl, o13, code, n, status, flags, (uint32_t)r.iters);
+        __builtin_amdgcn_wave_barrier();
+    };
+    for_each_dist_pair<G, G * K, TIER>(grp, a, body);
+}
+#endif  // GK_IN(12)
+
 }  // namespace gk
 
 // ---------------------------------------------------------------- host-side launch table
 // The product build compiles this file once per part (Makefile: -DGK_PART=p), each object instantiating
 // only its own kernels so the parts compile in parallel: 0 = chain reset, query service and the launch
 // dispatchers, 1 = one-wave query path (fp64 compute), 2 = GJK tiers, 3 = contact tiers, 4 + t = EPA
-// tier t, 10 = one-wave query path (fp32 compute), 11 = fp32 redo.
+// tier t, 10 = one-wave query path (fp32 compute), 11 = fp32 redo, 12 = separation distance tiers.
 // Without GK_PART (diagnostic variant builds) one object holds every part.  The non-template kernels
 // (chain reset, query service) are defined in part 0 only.
 // the one-wave query path in fp32 compute (part 10)
@@ -2914,6 +3054,29 @@ hipError_t gjkepa_launch_gjk(int tier, int vert_dtype, int precision, const gjke
     return precision == GJKEPA_PREC_F64 ? gjk_any<double, double>(tier, a, s) : gjk_any<double, float>(tier, a, s);
 }
 
+#endif
+
+#if GK_IN(12)
+namespace {
+template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
+hipError_t launch_dist(const gjkepa_dist_args& a, hipStream_t s) {
+    auto kfn = gk::dist_kernel<TIn, G, K, MINW, LH, TIER>;
+    constexpr int GPW = 64 / G;
+    const size_t lds = gk::lds_stride<gk::Lds<double, TIn, G, K, 0, 0>, G>() * GPW;
+    const int grid = grid_cap<G>(a.n_pairs, grid_for(kfn, lds, a.num_cus, a.grid));
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(64), lds, s, a);
+    return hipGetLastError();
+}
+template <typename TIn> hipError_t dist_any(int tier, const gjkepa_dist_args& a, hipStream_t s) {
+    static_assert(GJKEPA_GJK_TIERS == 3 && GJKEPA_G2_G * GJKEPA_G2_K >= GJKEPA_MAX_HULL_VERTS, "the last tier holds every hull");
+    return tier == 0 ? launch_dist<TIn, GJKEPA_G0_G, GJKEPA_G0_K, GJKEPA_D0_MINW, (GJKEPA_G0_LH != 0), 0>(a, s)
+         : tier == 1 ? launch_dist<TIn, GJKEPA_G1_G, GJKEPA_G1_K, GJKEPA_D1_MINW, (GJKEPA_G1_LH != 0), 1>(a, s)
+                     : launch_dist<TIn, GJKEPA_G2_G, GJKEPA_G2_K, GJKEPA_D2_MINW, (GJKEPA_G2_LH != 0), 2>(a, s);
+}
+}  // namespace
+hipError_t gjkepa_launch_dist(int tier, int vert_dtype, const gjkepa_dist_args& a, hipStream_t s) {
+    return vert_dtype == GJKEPA_DTYPE_F32 ? dist_any<float>(tier, a, s) : dist_any<double>(tier, a, s);
+}
 #endif
 
 #if GK_IN(3)

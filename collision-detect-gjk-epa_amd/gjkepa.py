@@ -22,6 +22,8 @@ LIB_PATH = os.path.join(_HERE, "build", "libgjkepa_hip.so")
 FLIB_PATH = os.path.join(_HERE, "build", "libgclib_gjkepa.so")
 
 STATUS_OK, STATUS_EPA_MAXITER, STATUS_DEGENERATE, STATUS_BAD_VERSION, STATUS_BAD_INPUT = 0, 1, 2, 3, 4
+STATUS_DIST_MAXITER = 5                      # distance records only (gjkepa_distance_batch)
+DIST_OVERLAP, DIST_HIT, DIST_FAR = 1, 2, 4   # distance record flag bits
 DTYPE_F32, DTYPE_F64 = 0, 1
 PREC_F32, PREC_F64 = 0, 1
 MAX_HULL_VERTS = 256
@@ -37,6 +39,8 @@ EXPORTS = (
     "gjkepa_comm_destroy", "gjkepa_comm_backend", "gjkepa_allgather_records_device",
     "gjkepa_query_service_stop", "gjkepa_query_service_set", "gjkepa_query_service_resident", "gjkepa_workspace_bytes_for",
     "gjkepa_launch_timing", "gjkepa_launch_timing_read",
+    "gjkepa_distance_record_bytes", "gjkepa_distance_workspace_bytes", "gjkepa_distance_batch_device",
+    "gjkepa_distance_batch",
 )
 COMM_ID_BYTES = 128
 # workspace header word counting the park slots a gjkepa_batch_device call took (diagnostics; csrc/
@@ -56,6 +60,13 @@ REC32 = np.dtype([
     ("reserved", "i1"), ("diag", "<u4"), ("pad", "<u4"),
 ])
 assert REC64.itemsize == 128 and REC32.itemsize == 64
+# gjkepa_distance_f64 (include/gjkepa.h): one per pair from distance_batch / distance_batch_device
+DIST64 = np.dtype([
+    ("distance", "<f8"), ("point_a", "<f8", (3,)), ("point_b", "<f8", (3,)), ("normal", "<f8", (3,)),
+    ("lambda", "<f8", (3,)), ("code", "<u4", (3,)), ("n_simplex", "i1"), ("status", "i1"), ("flags", "i1"),
+    ("reserved", "i1"), ("iters", "<u4"), ("pad", "<u4"),
+])
+assert DIST64.itemsize == 128
 
 
 def record_dtype(precision: int) -> np.dtype:
@@ -154,6 +165,16 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.gjkepa_launch_timing.restype = ctypes.c_int
     lib.gjkepa_launch_timing_read.argtypes = [c_vp, c_i32]
     lib.gjkepa_launch_timing_read.restype = ctypes.c_int
+    lib.gjkepa_distance_record_bytes.argtypes = []
+    lib.gjkepa_distance_record_bytes.restype = ctypes.c_int
+    lib.gjkepa_distance_workspace_bytes.argtypes = [c_i64]
+    lib.gjkepa_distance_workspace_bytes.restype = c_i64
+    lib.gjkepa_distance_batch_device.argtypes = [c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_dbl, c_vp, c_vp,
+                                                 c_i64, c_vp]
+    lib.gjkepa_distance_batch_device.restype = ctypes.c_int
+    lib.gjkepa_distance_batch.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_dbl, c_vp,
+                                          c_i32]
+    lib.gjkepa_distance_batch.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -357,6 +378,50 @@ def gjkepa_batch_warm_device(version: int, tol_ff: float, vert_dtype: int, preci
                                          hull_off_ptr, hull_cnt_ptr, pairs_ptr, int(n_pairs), out_ptr, ws_ptr,
                                          int(ws_bytes), warm_ptr, stream or None)
     _check(rc, "gjkepa_batch_warm_device")
+
+
+# ---- separation distance of non-colliding pairs (include/gjkepa.h gjkepa_distance_*) -------------------
+def distance_workspace_bytes(n_pairs: int) -> int:
+    b = int(load().gjkepa_distance_workspace_bytes(int(n_pairs)))
+    if b < 0:
+        raise GjkEpaError("gjkepa_distance_workspace_bytes: bad arguments")
+    return b
+
+
+def distance_batch(pool: HullPool, records: np.ndarray | None = None, max_distance: float = float("inf"),
+                   device: int = 0) -> np.ndarray:
+    """Separation distance and closest points of every pair of the pool (host buffers, blocking);
+    returns DIST64 records.  records: the pool's contact records (gjkepa_batch output, REC64 or REC32):
+    pairs they call a collision are skipped (flag DIST_HIT); None: overlaps are found here (DIST_OVERLAP).
+    max_distance: pairs proven farther apart stop early (flag DIST_FAR, distance = the lower bound)."""
+    lib = load()
+    out = np.zeros(pool.n_pairs, dtype=DIST64)
+    verts = np.ascontiguousarray(pool.verts)
+    off = np.ascontiguousarray(pool.hull_off, np.int64)
+    cnt = np.ascontiguousarray(pool.hull_cnt, np.int32)
+    prs = np.ascontiguousarray(pool.pairs, np.int32).reshape(-1)
+    rec_ptr, rec_prec = None, PREC_F64
+    if records is not None:
+        records = np.ascontiguousarray(records)
+        if records.dtype not in (REC64, REC32) or records.shape != (pool.n_pairs,):
+            raise GjkEpaError("records: one REC64 / REC32 contact record per pair")
+        rec_ptr, rec_prec = _ptr(records), (PREC_F64 if records.dtype == REC64 else PREC_F32)
+    rc = lib.gjkepa_distance_batch(pool.dtype_code, _ptr(verts), verts.size, _ptr(off), _ptr(cnt), cnt.size, _ptr(prs),
+                                   pool.n_pairs, rec_ptr, rec_prec, float(max_distance), _ptr(out), int(device))
+    _check(rc, "gjkepa_distance_batch")
+    return out
+
+
+def distance_batch_device(vert_dtype: int, verts_ptr: int, hull_off_ptr: int, hull_cnt_ptr: int, pairs_ptr: int,
+                          n_pairs: int, records_ptr: int, records_precision: int, max_distance: float, out_ptr: int,
+                          ws_ptr: int, ws_bytes: int, stream: int = 0) -> None:
+    """Device-resident distance query (raw device pointers), asynchronous on `stream`; records_ptr 0 /
+    None: no contact records.  Chain it after gjkepa_batch_device on the same stream with that call's
+    output as the records."""
+    rc = load().gjkepa_distance_batch_device(int(vert_dtype), verts_ptr, hull_off_ptr, hull_cnt_ptr, pairs_ptr,
+                                             int(n_pairs), records_ptr or None, int(records_precision),
+                                             float(max_distance), out_ptr, ws_ptr, int(ws_bytes), stream or None)
+    _check(rc, "gjkepa_distance_batch_device")
 
 
 # ---- multi-GPU (SURVEY.md §8 row e; include/gjkepa.h gjkepa_shard_range / _batch_multi / _comm_*) ------

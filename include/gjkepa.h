@@ -309,6 +309,80 @@ int gjkepa_batch_warm_device(int32_t version, double tol_ff, int32_t vert_dtype,
                              void* out, void* workspace, int64_t workspace_bytes,
                              uint32_t* warm, void* stream);
 
+/* ---- separation distance of non-colliding pairs -----------------------------------------------
+ * The other half of the narrow phase: for every pair of a batch that does not collide, how far apart
+ * the two hulls are and which two points are closest (speculative contacts, contact margins, step
+ * control, clearance).  The reference has no such query: GJKEPA leaves nearest_points_ at 0 for a miss
+ * (GCLIB_GJKEPA.f90:66-77, :87, :125).  This is a distance GJK in fp64 (vertices stored as fp32 or
+ * fp64) on the GJK tiers' group shapes, independent of the contact records' bit-exact recipe:
+ *   v = a_0 - b_0; each iteration takes the support point w of A - B along -v (first maximum on ties),
+ *   stops when the gap v.v - v.w is within 1e-10 v.v or w is already a simplex vertex, and otherwise
+ *   replaces the simplex by its sub-simplex closest to the origin (at most 3 vertices).  A tetrahedron
+ *   around the origin, or |v| below 1e-12 of the simplex's scale, is an overlap.  There is no sphere
+ *   pre-test exit, and at most 64 iterations (then GJKEPA_STATUS_DIST_MAXITER with the bounds so far).
+ * max_distance: every iteration has the lower bound lb = v.w / |v|; a pair stops as soon as
+ *   lb > max_distance, flagged FAR with distance = lb (so FAR means exactly that the last lower bound
+ *   exceeds max_distance, also for a pair that would have converged in that iteration).  +inf: none.
+ * records: NULL, or the contact records gjkepa_batch_device wrote for the same pair list (precision
+ *   records_precision).  Pairs whose collision byte is set are not computed: flag HIT, distance 0.
+ *   With NULL the kernel finds overlapping pairs itself and flags them OVERLAP.
+ *
+ * One record per pair.  A separated pair's record certifies itself: point_a = sum_k lambda[k] a[ia_k]
+ * and point_b = sum_k lambda[k] b[ib_k] (ia_k | ib_k << 16 = code[k], lambda >= 0, sum 1) lie in the
+ * hulls, so |point_a - point_b| bounds the distance from above, and min_i normal.a_i - max_j normal.b_j
+ * bounds it from below.
+ *   distance   separation; 0 for OVERLAP / HIT; the lower bound lb for FAR
+ *   point_a/b  closest points on hull A / hull B (FAR: of the simplex so far; 0 for OVERLAP / HIT)
+ *   normal     (point_a - point_b) / |point_a - point_b|, unit; 0 when distance is 0
+ *   lambda     barycentric weights of the final simplex (unused entries 0)
+ *   code       ia | ib << 16 per simplex vertex, the warm-start convention (unused 0xFFFFFFFF)
+ *   n_simplex  1..3 (0 when not separated)
+ *   status     GJKEPA_STATUS_OK, _BAD_INPUT (the batch's rules) or _DIST_MAXITER
+ *   flags      GJKEPA_DIST_OVERLAP | _HIT | _FAR
+ *   iters      GJK iterations */
+#define GJKEPA_STATUS_DIST_MAXITER 5  /* distance GJK hit its 64-iteration cap: best bounds so far */
+#define GJKEPA_DIST_OVERLAP 1   /* the hulls overlap or touch (found by the distance kernel itself) */
+#define GJKEPA_DIST_HIT     2   /* skipped: the pair's contact record says collision */
+#define GJKEPA_DIST_FAR     4   /* stopped early: the lower bound in `distance` exceeds max_distance */
+typedef struct gjkepa_distance_f64 {
+    double   distance;
+    double   point_a[3];
+    double   point_b[3];
+    double   normal[3];
+    double   lambda[3];
+    uint32_t code[3];
+    int8_t   n_simplex;
+    int8_t   status;
+    int8_t   flags;
+    int8_t   reserved;
+    uint32_t iters;
+    uint32_t pad;
+} gjkepa_distance_f64;           /* 128 bytes */
+
+/* Size in bytes of one distance record (128). */
+int gjkepa_distance_record_bytes(void);
+/* Bytes of device workspace for n_pairs pairs (the tier launches' work counters, reset by the call
+ * itself; 256-byte aligned); negative for n_pairs < 0. */
+int64_t gjkepa_distance_workspace_bytes(int64_t n_pairs);
+/* Device buffers, asynchronous on `stream` (hipStream_t or NULL): no allocation, no synchronisation,
+ * every launch on that stream only (a captured graph is a linear chain).  The natural pipeline is
+ * gjkepa_batch_device followed by this call on the same stream with `records` = the batch's `out`.
+ * Deterministic: no atomics touch results.  Records nothing for gjkepa_launch_timing.
+ * GJKEPA_E_ARG for a bad dtype, a bad records_precision with records != NULL, a null pointer, or a NaN
+ * or negative max_distance; GJKEPA_E_WORKSPACE for a workspace below gjkepa_distance_workspace_bytes. */
+int gjkepa_distance_batch_device(int32_t vert_dtype, const void* verts, const int64_t* hull_off,
+                                 const int32_t* hull_cnt, const int32_t* pairs, int64_t n_pairs,
+                                 const void* records, int32_t records_precision,
+                                 double max_distance, void* out, void* workspace, int64_t workspace_bytes,
+                                 void* stream);
+/* Host buffers, blocking; the pool arguments and checks of gjkepa_batch.  records: NULL or n_pairs
+ * contact records (host memory) of precision records_precision. */
+int gjkepa_distance_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
+                          const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                          const int32_t* pairs, int64_t n_pairs,
+                          const void* records, int32_t records_precision, double max_distance,
+                          void* out, int32_t device);
+
 /* ---- whole collision step (host buffers, blocking) ---------------------------------------------
  * The reference caller's `DO a; DO b = a+1; CALL GJKEPA(...)` over a pooled hull set in one call:
  * gjkepa_broadphase_device -> gjkepa_batch_device on the candidate list -> gjkepa_compact_hits_device.
