@@ -176,6 +176,12 @@
 #ifndef GJKEPA_C1_MINW
 #define GJKEPA_C1_MINW 3        // A/B r5 (2 rounds): 2 -> 3 waves/SIMD C4 39.9 -> 40.6, C5 23.1 -> 23.5 M/s, C2 unchanged
 #endif
+// Contact tiers with more than one group per wave (tier 0): case_04 pairs finish everything but the
+// branch's body in the main round and wait on a per-wave LDS queue until 64 / G of them fill a round of
+// their own (gjkepa_kernel.hip, contact_kernel).  0: every pair runs case_04 in its main round (A/B).
+#ifndef GJKEPA_CT_QUEUE04
+#define GJKEPA_CT_QUEUE04 1
+#endif
 // Seed hand-over (fp64 compute only).  A GJK hit from the tetrahedron code leaves, beside the simplex
 // codes, the four unit face normals of its final simplex in the pair's record slot, and a flag that
 // says whether EPA may take them:

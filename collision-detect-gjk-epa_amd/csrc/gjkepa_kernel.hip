@@ -184,7 +184,7 @@ DEV void guard_report(uint32_t kid, uint32_t want, uint32_t got) {
 
 enum { SG_LOAD = 0, SG_SPHERE, SG_INIT, SG_UPD, SG_CHK, SG_STORE, SG_ROUTE,
        SE_LOAD = 10, SE_IT1, SE_DIR, SE_SUP, SE_VIS, SE_HOR, SE_CMP, SE_CONE, SE_TERM, SE_NEAR, SE_CONT, SE_TYPE,
-       SE_STORE, SE_ROUTE, SC_ROUTE, SC_LOAD, SC_STORE };
+       SE_STORE, SE_ROUTE, SC_ROUTE, SC_LOAD, SC_STORE, SC_CASE04 };
 
 
 // ---------------------------------------------------------------- per-group LDS image
@@ -1472,8 +1472,15 @@ CTX_T DEV int contact_case04(CTX& c, int na, V3<T> b0, V3<T> b1, V3<T>& res) {
     return 0;
 }
 
-// get_collisionPoint_02 (:457-696)
-CTX_T DEV int contact_v2(CTX& c, const DotSet<T, K>& D, V3<T>& res) {
+// A case_04 pair whose body the caller runs later (contact tier 0's pending queue, contact_kernel):
+// which hull the polygon set is from, its size, and the 2-point set's two hull-vertex indices.  The
+// polygon set's vertex list is left in si[0..na).
+struct Pend04 { bool on; int side, na, q0, q1; };
+
+// get_collisionPoint_02 (:457-696).  DEFER: a case_04 pair stores both band sets and is described in
+// *pd instead of running contact_case04 (res stays zero).
+template <bool DEFER = false, typename T, typename TH, int G, int K, int VC, int FC, int LH>
+DEV int contact_v2(CTX& c, const DotSet<T, K>& D, V3<T>& res, Pend04* pd = nullptr) {
     const T band = T(0.1);
     const T t1 = D.m[0] - band, t2 = D.m[1] - band;                 // :471-472
     const int n1 = band_set(c, 0, D, t1, false);
@@ -1501,16 +1508,32 @@ CTX_T DEV int contact_v2(CTX& c, const DotSet<T, K>& D, V3<T>& res) {
         res = vdiv(vadd(f1, f2), T(2));
     } else if (n1 == 2 && n2 >= 3) {                               // case_04(SPT_p2, SPT_p1)
         band_set(c, 0, D, t1, true);
+        if constexpr (DEFER) {
+            const int i0 = c.L.u.c.si[0] & 0x7fff, i1 = c.L.u.c.si[1] & 0x7fff;
+            __builtin_amdgcn_wave_barrier();
+            band_set(c, 1, D, t2, true);
+            *pd = Pend04{true, 1, n2, i0, i1};
+            return 0;
+        } else {
         const V3<T> q0 = set_pt(c, 0), q1 = set_pt(c, 1);
         __builtin_amdgcn_wave_barrier();
         band_set(c, 1, D, t2, true);
         return contact_case04(c, n2, q0, q1, res);
+        }
     } else if (n1 >= 3 && n2 == 2) {                               // case_04(SPT_p1, SPT_p2)
         band_set(c, 1, D, t2, true);
+        if constexpr (DEFER) {
+            const int i0 = c.L.u.c.si[0] & 0x7fff, i1 = c.L.u.c.si[1] & 0x7fff;
+            __builtin_amdgcn_wave_barrier();
+            band_set(c, 0, D, t1, true);
+            *pd = Pend04{true, 0, n1, i0, i1};
+            return 0;
+        } else {
         const V3<T> q0 = set_pt(c, 0), q1 = set_pt(c, 1);
         __builtin_amdgcn_wave_barrier();
         band_set(c, 0, D, t1, true);
         return contact_case04(c, n1, q0, q1, res);
+        }
     } else if (n1 >= 3 && n2 >= 3) {                               // case_05
         band_set(c, 0, D, t1, true);
         T sx = 0, sy = 0, sz = 0;
@@ -1798,8 +1821,9 @@ CTX_T DEV int epa_phase(CTX& c, const uint32_t* kc, T& depth, V3<T>& n, uint32_t
 }
 
 // EPA_solu's post-processing (:326-343) for EPA depth and normal n: nearest points, contact point
-// (version_ 1/2/3) and contact type.  Returns -type (o13 filled) or an error status.
-CTX_T DEV int contact_phase(CTX& c, T depth, V3<T> n, int version, T tol_ff, T* o13) {
+// (version_ 1/2/3) and contact type.  Returns -type (o13 filled) or an error status.  DEFER: see contact_v2.
+template <bool DEFER = false, typename T, typename TH, int G, int K, int VC, int FC, int LH>
+DEV int contact_phase(CTX& c, T depth, V3<T> n, int version, T tol_ff, T* o13, Pend04* pd = nullptr) {
     int st;
     int ia, ib;
     GK_STAMP(SE_TERM);
@@ -1813,7 +1837,7 @@ CTX_T DEV int contact_phase(CTX& c, T depth, V3<T> n, int version, T tol_ff, T* 
     // contact point, so the dots are dead during case_04 (the contact kernel's register peak)
     int type = (version == 1 || version == 2) ? collision_type(c, D, tol_ff) : 0;
     if (version == 1) st = contact_v1(c, n, D, pt);                       // :329-340
-    else if (version == 2) st = contact_v2(c, D, pt);
+    else if (version == 2) st = contact_v2<DEFER>(c, D, pt, pd);
     else if (version == 3) { V3<T> nw; st = contact_v3(c, n, pt, nw); n = nw; }
     else st = GJKEPA_STATUS_BAD_VERSION;
     GK_STAMP(SE_CONT);
@@ -1929,9 +1953,11 @@ DEV int64_t shfl64(int64_t v, int src) {
     const int lo = __shfl((int)(uint32_t)(uint64_t)v, src), hi = __shfl((int)(uint32_t)((uint64_t)v >> 32), src);
     return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
 }
-template <int G, bool META = false, typename F>
+// `after` runs once per round on the whole wave, outside the `if (active)` of the groups that took a pair.
+struct NoRoundHook { DEV void operator()() const {} };
+template <int G, bool META = false, typename F, typename R = NoRoundHook>
 DEV void groups_take(const Grp<G>& grp, int64_t p0, uint64_t m, const int32_t* pairs, const int32_t* cnt,
-                     const int64_t* off, F&& f) {
+                     const int64_t* off, F&& f, R&& after = R{}) {
     constexpr int GPW = 64 / G;
     const int gid = grp.lane / G;
     PairMeta mine{0, 0, 0, 0};
@@ -1957,6 +1983,7 @@ DEV void groups_take(const Grp<G>& grp, int64_t p0, uint64_t m, const int32_t* p
         } else {
             if (active) f(p0 + bit);
         }
+        after();
     }
 }
 // 16-bit mask of this lane's 16 route bytes equal to code
@@ -2018,10 +2045,10 @@ DEV int pick_claim(const uint32_t* tally, int route_code, int64_t n_pairs, int c
     return (int64_t)mine * 16 >= n_pairs ? 1 : claim;
 }
 
-template <int G, bool META = false, typename F>
+template <int G, bool META = false, typename F, typename R = NoRoundHook>
 DEV void for_each_routed_pair(const Grp<G>& grp, int64_t n_pairs, const uint8_t* __restrict__ route, int route_code,
                               uint32_t* ctr, int claim, bool unit_grid, F&& f, const int32_t* pairs = nullptr,
-                              const int32_t* cnt = nullptr, const int64_t* off = nullptr) {
+                              const int32_t* cnt = nullptr, const int64_t* off = nullptr, R&& after = R{}) {
     // the first unit of workgroup b is unit b; later units come from the counter (offset by the
     // grid), so a launch with fewer units than workgroups issues no atomics at all.  unit_grid: the
     // launch has one workgroup per 64-pair chunk (dense launches only): a workgroup takes its own
@@ -2035,7 +2062,7 @@ DEV void for_each_routed_pair(const Grp<G>& grp, int64_t n_pairs, const uint8_t*
             const int len = n_pairs - p0 < 64 ? (int)(n_pairs - p0) : 64;
             const uint64_t m = route_code < 0 ? (len >= 64 ? ~0ull : ((1ull << len) - 1ull))
                                               : __ballot(grp.lane < len && (int)route[p0 + grp.lane] == route_code);
-            groups_take<G, META>(grp, p0, m, pairs, cnt, off, f);
+            groups_take<G, META>(grp, p0, m, pairs, cnt, off, f, after);
         }
         return;
     }
@@ -2055,7 +2082,7 @@ DEV void for_each_routed_pair(const Grp<G>& grp, int64_t n_pairs, const uint8_t*
                 const int64_t p = p0 + grp.lane;
                 m = __ballot(grp.lane < len && (int)route[p] == route_code);
             }
-            groups_take<G, META>(grp, p0, m, pairs, cnt, off, f);
+            groups_take<G, META>(grp, p0, m, pairs, cnt, off, f, after);
             u = (int64_t)__builtin_amdgcn_readfirstlane(next);
         }
         return;
@@ -2084,7 +2111,7 @@ DEV void for_each_routed_pair(const Grp<G>& grp, int64_t n_pairs, const uint8_t*
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 m |= (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)mine, 4 * j + i) << (16 * i);
-            groups_take<G, META>(grp, run * 1024 + 64 * j, m, pairs, cnt, off, f);
+            groups_take<G, META>(grp, run * 1024 + 64 * j, m, pairs, cnt, off, f, after);
         }
     }
 }
@@ -2639,6 +2666,96 @@ __global__ __launch_bounds__(64, GJKEPA_SVC_MINW) void service_kernel(const gjke
 
 // Contact kernel: nearest points, contact point and contact type (:326-343) for every pair EPA
 // finished, from the depth and normal it parked; writes the final record.
+//
+// Pending case_04 queue (GJKEPA_CT_QUEUE04; kernels with more than one group per wave: tier 0).
+// contact_v2 branches per group and case_04 (SORT_CLOCK: an atan2 and an fmod per candidate and step,
+// then two polygon-inside tests) is its one long branch: about 28% of C2's hits take it, so nearly every
+// round of 64 / G pairs holds one and the wave pays for it with under a third of its groups working.
+// A group whose pair takes case_04 finishes everything else in the main round (dots, nearest points,
+// contact type, both band sets, the record with a zero contact point) and pushes what the branch needs
+// onto a per-wave LDS queue: the pair, its hulls' offsets and counts, and the vertex indices of the
+// polygon set (in band-set order, SORT_CLOCK's input order) and of the 2-point set.  Once 64 / G
+// entries are pending, a deferred round runs them on all groups: each group loads only its entry's
+// na + 2 vertices (in L2: the wave has just read them), lays them out as a hull image of its own
+// (polygon at slots 0..na-1 of its side, the two points at slots 0 and 1 of the other) and runs the
+// same contact_case04 through set_pt, so the conversions and the bits are the main round's.  It then
+// writes the contact point over the record's three zero words (or the zero record with case_04's error
+// status; fp32 compute: the redo route) and only then the pair's route byte.  The queue lives across
+// the wave's units; what is left when the wave runs out of units takes one last partial round.
+template <int NH> struct Pend04Entry {
+    static_assert(NH < 256, "vertex indices and the set size are kept as bytes");
+    int64_t pair, oa, ob;        // pair index; vertex offsets of hull A / B
+    uint32_t diag;               // the record's diag word
+    uint16_t ca, cb;             // vertex counts of hull A / B
+    uint8_t side, na, q0, q1;    // polygon set: hull and size; 2-point set: its two vertices (other hull)
+    uint8_t idx[NH];             // polygon set's vertices in band-set order
+};
+// main rounds leave at most 64 / G - 1 entries behind and add at most 64 / G: 2 (64 / G) - 1 are held
+template <int G, int K> struct Pend04Queue {
+    static constexpr int CAP = 2 * (64 / G);                      // ring slots (a power of two)
+    Pend04Entry<G * K> e[CAP];
+};
+template <int G> constexpr bool ct_queue04() { return GJKEPA_CT_QUEUE04 != 0 && G < 64; }
+template <typename TIn, typename T, int G, int K> constexpr size_t contact_lds_bytes() {
+    size_t bytes = lds_stride<Lds<T, TIn, G, K, 0, 1>, G>() * (64 / G);       // the groups' images
+    if constexpr (ct_queue04<G>()) bytes += sizeof(Pend04Queue<G, K>);        // then the queue
+    return bytes;
+}
+
+// One deferred round: group g takes pending entry g of the ring from `qhead` on (g < cnt <= 64 / G).
+// A function of its own, not inlined: it runs once per 64 / G case_04 pairs, and inlined at its uses
+// (one per scheduling form of for_each_routed_pair and the last partial round) its registers stacked on
+// the main round's (168 VGPRs with 24 spilled).  It finds the wave's LDS by name, like the kernel, so
+// its LDS accesses stay ds_ instructions.
+template <typename TIn, typename T, int G, int K, bool LH>
+__device__ __noinline__ void case04_round(int qhead, int cnt, const TIn* verts, void* out, uint8_t* route) {
+    using L_t = Lds<T, TIn, G, K, 0, 1>;
+    using Q_t = Pend04Queue<G, K>;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const Grp<G> grp;
+    const int gl = grp.gl, g = grp.lane / G;
+    L_t& L = *reinterpret_cast<L_t*>(smem + lds_stride<L_t, G>() * g);
+    const Q_t& Q = *reinterpret_cast<const Q_t*>(smem + lds_stride<L_t, G>() * (64 / G));
+    if (g < cnt) {
+        const auto& e = Q.e[(qhead + g) & (Q_t::CAP - 1)];
+        const int64_t pair = e.pair;
+        const int side = e.side, na = e.na;
+        const int cp = side ? e.cb : e.ca, co = side ? e.ca : e.cb;
+        const TIn* pp = verts + (side ? e.ob : e.oa);       // the polygon set's hull
+        const TIn* po = verts + (side ? e.oa : e.ob);       // the 2-point set's hull
+        for (int i = gl; i < na; i += G) {
+            const int j = e.idx[i];
+            L.hx[side][i] = pp[j]; L.hy[side][i] = pp[cp + j]; L.hz[side][i] = pp[2 * cp + j];
+            L.u.c.si[i] = (uint16_t)(i | (side << 15));
+        }
+        if (gl < 2) {
+            const int j = gl ? e.q1 : e.q0;
+            L.hx[1 - side][gl] = po[j]; L.hy[1 - side][gl] = po[co + j]; L.hz[1 - side][gl] = po[2 * co + j];
+        }
+        __builtin_amdgcn_wave_barrier();
+        Ctx<T, TIn, G, K, 0, 1, LH> c{L, grp};
+        c.na = e.ca;
+        c.nb = e.cb;
+        const V3<T> b0 = side ? c.A(0) : c.B(0), b1 = side ? c.A(1) : c.B(1);
+        V3<T> res = zero3<T>();
+        const int r = contact_case04(c, na, b0, b1, res);
+        __builtin_amdgcn_wave_barrier();
+        uint8_t next = 0;
+        if (r == 0) {
+            if (gl < 3) reinterpret_cast<T*>(out)[pair * 16 + 4 + gl] = gl == 0 ? res.x : gl == 1 ? res.y : res.z;
+        } else if (redo_status<T>(r, false)) {   // fp32: case_04's error status, recomputed in fp64
+            next = GJKEPA_ROUTE_REDO;
+        } else {                                 // error status: outputs zero, collision = 1
+            T o13[13];
+#pragma unroll
+            for (int i = 0; i < 13; ++i) o13[i] = T(0);
+            store_record<G, T>(out, pair, gl, o13, 1, 0, r, e.diag);
+        }
+        if (gl == 0) { route[pair] = next; if (next) tally_route(next); }
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
 template <typename TIn, typename T, int G, int K, int MINW, bool LH>
 __global__ __launch_bounds__(64, MINW) void contact_kernel(const gjkepa_epa_args a) {
     using L_t = Lds<T, TIn, G, K, 0, 1>;
@@ -2652,6 +2769,12 @@ __global__ __launch_bounds__(64, MINW) void contact_kernel(const gjkepa_epa_args
     if (tier_empty(a.tally, a.route_code)) return;
     tally_begin();
     const int claim = pick_claim(a.tally, a.route_code, a.n_pairs, a.claim);
+    constexpr bool Q04 = ct_queue04<G>();
+    constexpr int GPW = 64 / G;
+    using Q_t = Pend04Queue<G, K>;
+    static_assert(lds_stride<L_t, G>() % 8 == 0, "the queue follows the images, 8-byte aligned");
+    [[maybe_unused]] int qhead = 0, qn = 0;    // Q04, wave-uniform: first pending slot, entries pending
+    [[maybe_unused]] bool pushed = false;      // Q04: this group pushed an entry in the current main round
     auto body = [&](int64_t pair, const PairMeta& pm) {
         GK_STAMP(SC_ROUTE);
         Ctx<T, TIn, G, K, 0, 1, LH> c{L, grp};
@@ -2664,16 +2787,17 @@ __global__ __launch_bounds__(64, MINW) void contact_kernel(const gjkepa_epa_args
         load_hulls(c, verts + pm.oa, verts + pm.ob);
         GK_STAMP(SC_LOAD);
         T o13[13];
+        [[maybe_unused]] Pend04 pd{false, 0, 0, 0, 0};
 #ifdef GJKEPA_DIAG_NO_CONTACT   // timing ablation only
         const int r = -1;
 #pragma unroll
         for (int i = 0; i < 13; ++i) o13[i] = T(0);
 #else
-        const int r = contact_phase(c, depth, n, a.version, (T)a.tol_ff, o13);
+        const int r = contact_phase<Q04>(c, depth, n, a.version, (T)a.tol_ff, o13, &pd);
 #endif
         __builtin_amdgcn_wave_barrier();
         uint8_t next = 0;
-        if (r < 0) {
+        if (r < 0) {                 // a case_04 pair that waits too: its contact point is zero for now
             store_record<G, T>(a.out, pair, gl, o13, 1, -r, 0, diag);
         } else if (redo_status<T>(r, false)) {   // fp32: contact-phase error, recomputed in fp64
             next = GJKEPA_ROUTE_REDO;
@@ -2682,13 +2806,53 @@ __global__ __launch_bounds__(64, MINW) void contact_kernel(const gjkepa_epa_args
             for (int i = 0; i < 13; ++i) o13[i] = T(0);
             store_record<G, T>(a.out, pair, gl, o13, 1, 0, r, diag);
         }
-        if (gl == 0) { a.route[pair] = next; if (next) tally_route(next); }
+        if constexpr (Q04) {
+            // the groups of this round that push, lowest first, take consecutive slots behind the queue;
+            // their route bytes wait for the deferred round
+            Q_t& Q = *reinterpret_cast<Q_t*>(smem + lds_stride<L_t, G>() * GPW);
+            const uint64_t pushing = __ballot(pd.on);
+            if (pd.on) {
+                const int rank = popc(pushing & ((1ull << (grp.lane & ~(G - 1))) - 1ull)) / G;
+                auto& e = Q.e[(qhead + qn + rank) & (Q_t::CAP - 1)];
+                for (int i = gl; i < pd.na; i += G) e.idx[i] = (uint8_t)(L.u.c.si[i] & 0x7fff);
+                if (gl == 0) {
+                    e.pair = pair; e.oa = pm.oa; e.ob = pm.ob;
+                    e.diag = diag;
+                    e.ca = (uint16_t)c.na; e.cb = (uint16_t)c.nb;
+                    e.side = (uint8_t)pd.side; e.na = (uint8_t)pd.na; e.q0 = (uint8_t)pd.q0; e.q1 = (uint8_t)pd.q1;
+                }
+                pushed = true;
+            } else if (gl == 0) {
+                a.route[pair] = next;
+                if (next) tally_route(next);
+            }
+        } else {
+            if (gl == 0) { a.route[pair] = next; if (next) tally_route(next); }
+        }
         __builtin_amdgcn_wave_barrier();
         GK_STAMP(SC_STORE);
     };
-    for_each_routed_pair<G, true>(grp, a.n_pairs, a.route, a.route_code, a.ctr, claim, a.grid == GJKEPA_GRID_UNITS, body,
-                                  a.pairs, a.hull_cnt, a.hull_off);
-    GK_STAMP(SC_ROUTE);
+    if constexpr (Q04) {
+        auto deferred = [&](int cnt) __attribute__((always_inline)) {
+            case04_round<TIn, T, G, K, LH>(qhead, cnt, verts, a.out, a.route);
+            qhead = (qhead + cnt) & (Q_t::CAP - 1);
+            qn -= cnt;
+            GK_STAMP(SC_CASE04);
+        };
+        auto after = [&]() __attribute__((always_inline)) {   // per round: count the pushes, run a full round
+            qn += popc(__ballot(pushed)) / G;
+            pushed = false;
+            if (qn >= GPW) deferred(GPW);
+        };
+        for_each_routed_pair<G, true>(grp, a.n_pairs, a.route, a.route_code, a.ctr, claim, a.grid == GJKEPA_GRID_UNITS, body,
+                                      a.pairs, a.hull_cnt, a.hull_off, after);
+        GK_STAMP(SC_ROUTE);
+        if (qn > 0) deferred(qn);        // no further unit: the last partial round
+    } else {
+        for_each_routed_pair<G, true>(grp, a.n_pairs, a.route, a.route_code, a.ctr, claim, a.grid == GJKEPA_GRID_UNITS, body,
+                                      a.pairs, a.hull_cnt, a.hull_off);
+        GK_STAMP(SC_ROUTE);
+    }
     tally_end(a.tally);
     GK_STAMP_END();
 }
@@ -2914,8 +3078,7 @@ hipError_t launch_epa(const gjkepa_epa_args& a, hipStream_t s) {
 template <typename TIn, typename T, int G, int K, int MINW, bool LH>
 hipError_t launch_contact(const gjkepa_epa_args& a, hipStream_t s) {
     auto kfn = gk::contact_kernel<TIn, T, G, K, MINW, LH>;
-    constexpr int GPW = 64 / G;
-    const size_t lds = gk::lds_stride<gk::Lds<T, TIn, G, K, 0, 1>, G>() * GPW;
+    const size_t lds = gk::contact_lds_bytes<TIn, T, G, K>();     // the groups' images, then the case_04 queue
     int grid;
     if (a.grid == GJKEPA_GRID_UNITS) {                  // one workgroup per 64-pair chunk (dense launches)
         grid = (int)((a.n_pairs + 63) / 64);

@@ -19,7 +19,7 @@ NAMES = {0: "gjk.load", 1: "gjk.sphere", 2: "gjk.init", 3: "gjk.update_simplex",
          5: "gjk.store", 6: "gjk.route", 10: "epa.load", 11: "epa.iter1", 12: "epa.dir", 13: "epa.support",
          14: "epa.visible", 15: "epa.horizon", 16: "epa.compact", 17: "epa.cone", 18: "epa.term",
          19: "ct.nearest", 20: "ct.contact", 21: "ct.type", 22: "epa.store", 23: "epa.route",
-         24: "ct.route", 25: "ct.load", 26: "ct.store"}
+         24: "ct.route", 25: "ct.load", 26: "ct.store", 27: "ct.case04"}
 
 
 def main():
