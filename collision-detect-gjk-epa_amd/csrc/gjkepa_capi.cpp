@@ -50,17 +50,12 @@ constexpr int kWsParkWord = GJKEPA_WS_COUNTERS + GJKEPA_WS_TALLY;
 constexpr int64_t kParkShare = 8;
 int64_t ws_base(int64_t n) { return (kWsHeader + n + 255) / 256 * 256; }
 constexpr int kSparseClaim = 16;
-#ifndef GJKEPA_OVERLAP_MIN
-#define GJKEPA_OVERLAP_MIN (1 << 16)
-#endif
-constexpr int64_t kOverlapMin = GJKEPA_OVERLAP_MIN;   // batches from this size fork the contact pass (enqueue)
-#ifndef GJKEPA_FUSED_MAX
-#define GJKEPA_FUSED_MAX 64
-#endif
-constexpr int64_t kFusedMax = GJKEPA_FUSED_MAX;       // batches up to this size run the one-kernel query path
-#ifndef GJKEPA_DENSE_EPA_TIERS
-#define GJKEPA_DENSE_EPA_TIERS 2   // EPA tiers below this always claim single chunks; the others start
-#endif                             // sparse and switch to single chunks when their route tally is dense   // tiers that serve few pairs claim runs of 16 chunks (one 1-KB route load)
+constexpr int64_t kOverlapMin = 1 << 16;   // batches from this size run the overlapped chain (enqueue)
+constexpr int64_t kFusedMax = 64;          // batches up to this size run the one-kernel query path
+// EPA tiers below this always claim single chunks; the others serve few pairs: they start sparse, in
+// runs of kSparseClaim chunks (one 1-KB route load), and switch to single chunks when their route
+// tally is dense
+constexpr int kDenseEpaTiers = 2;
 
 struct DevBuf {
     void* p = nullptr;
@@ -128,46 +123,42 @@ int num_cus_current() {
     return cus;
 }
 
-// Second stream for the overlapped contact passes.  The pairs EPA tier t
-// finishes carry the route codes GJKEPA_ROUTE_CT(t) + contact tier, and their contact pass is forked
-// onto an internal stream as soon as tier t is done, so it runs beside EPA tiers t+1..4: on C2 the
-// contact pass of EPA tier 0 (most of the hits) overlaps tier 1 (a few long pairs), on C5 that of
-// tier 2 overlaps tier 3.  Every fork joins back into the caller's stream at the end of the chain;
-// the two streams never touch the same pair.  The internal stream and its events belong to one
-// (device, caller stream): callers on different streams never share them, so one caller's work
-// never waits on another's contact passes, and an internal stream that joins a caller's graph
-// capture (the fork / join events make it part of the capture) carries only that caller's work.
-// Up to kForkMax caller streams get their own; further streams run the chain on one stream.
+// Internal streams of the overlapped chain (batches from kOverlapMin pairs; the schedule is the list in
+// enqueue).  The pairs EPA tier t finishes carry the route codes GJKEPA_ROUTE_CT(p) + contact tier,
+// where p is the first fork point at or after t, and the contact pass of fork point p is enqueued as
+// soon as tier p is done.  Fork points: after tier 0 (C2's hits), after tier 2 (C4 / C5's
+// 33-128-vertex hulls, with tier 1's few overflow pairs) and after the last tier (tiers 3-5): three
+// passes and five contact launches instead of up to two launches per tier, so the short tail of a C2
+// chain carries three fewer near-empty launches.  The passes of points 0 and 2 run on an internal
+// stream each, beside the EPA tiers that follow: on C2 the pass of EPA tier 0 (most of the hits)
+// overlaps tier 1 (a few long pairs), on C5 that of tier 2 overlaps tier 3, and a small pass forked
+// late does not queue behind the big pass of tier 0.  The last point's pass runs on the caller's
+// stream: nothing follows it to overlap.  Every internal stream joins back into the caller's at the
+// end of the chain; two streams never touch the same pair.
 // (A/B: the other way round, later EPA tiers on a high-priority internal stream beside the contact
 // pass, was 2.5% slower on C2.)
-// Each fork point gets its own internal stream (GJKEPA_FORK_STREAMS 2; 1: one shared stream, the
-// passes in order), so a small pass forked late does not queue behind the big pass of tier 0.  The
-// internal streams run at the highest stream priority (GJKEPA_FORK_PRIO 1; 0 default, -1 lowest):
-// the forked pass of EPA tier 0 is the C2 chain's critical path, while the EPA tiers beside it serve
-// a few long pairs (A/B r3: C2 144.5 vs 143.9 M/s at the lowest priority; C4 / C5 unchanged).  The last fork
-// point's pass runs on the caller's stream (GJKEPA_LAST_PASS_MAIN): nothing follows it to overlap.
-#ifndef GJKEPA_FORK_MASK
-#define GJKEPA_FORK_MASK 0x25
-#endif
-#ifndef GJKEPA_FORK_STREAMS
-#define GJKEPA_FORK_STREAMS 2
-#endif
-#ifndef GJKEPA_FORK_PRIO
-#define GJKEPA_FORK_PRIO 1
-#endif
-#ifndef GJKEPA_LAST_PASS_MAIN
-#define GJKEPA_LAST_PASS_MAIN 1
-#endif
+// The pass streams run at the highest stream priority: the pass of EPA tier 0 is the C2 chain's
+// critical path, while the EPA tiers beside it serve a few long pairs (A/B r3: C2 144.5 vs 143.9 M/s
+// at the lowest priority; C4 / C5 unchanged).
+// EPA tier 0 runs in two parts over consecutive pair ranges, the second on a third internal stream
+// (s3, default priority), and each part's pass is enqueued as soon as that part is done, so it runs
+// beside the other part's EPA instead of after all of tier 0 (C2's critical path was GJK 0 -> EPA 0 ->
+// the whole contact pass), and a part's tail overlaps the other part instead of idling the CUs it
+// leaves.  A/B r4 (C2, 2 rounds): 1 part 149.7, 2 parts 150.7, 4 parts 145.5, 8 parts 113.8 M/s; 2 parts
+// on one stream 150.7, on two streams 157.4 M/s.  Which launch answers a pair never changes its record.
+// The streams and events belong to one (device, caller stream): callers on different streams never
+// share them, so one caller's work never waits on another's contact passes, and an internal stream
+// that joins a caller's graph capture (the fork / join events make it part of the capture) carries
+// only that caller's work.  Up to kForkMax caller streams get their own; further streams run the
+// chain on one stream.
 struct Fork {
     std::mutex mu;
-    hipStream_t s2[GJKEPA_EPA_TIERS] = {};       // internal stream of fork point t (all [0] if shared)
-    hipEvent_t fork[GJKEPA_EPA_TIERS] = {}, join[GJKEPA_EPA_TIERS] = {};
-    hipEvent_t part[8] = {};                     // fork of EPA tier 0's (0..3) / tier 2's (4..7) part i
-    hipStream_t s3 = nullptr;                    // second stream for alternate parts (GJKEPA_EPA0_STREAMS 2)
-    hipEvent_t fork3 = nullptr, join3 = nullptr;
-    hipStream_t s4 = nullptr;                    // contact passes of the odd parts (GJKEPA_PART_PASS_STREAMS 2)
-    hipEvent_t join4 = nullptr;
-    hipEvent_t fork23 = nullptr, join23 = nullptr;   // EPA tier 3 on s3 beside tier 2 (GJKEPA_E23_STREAMS 2)
+    hipStream_t pass0 = nullptr, pass2 = nullptr;   // contact passes of fork points 0 and 2
+    hipStream_t s3 = nullptr;                       // EPA tier 0's second part
+    hipEvent_t fork3 = nullptr, join3 = nullptr;    // caller's stream -> s3 and back
+    hipEvent_t part[2] = {};                        // EPA tier 0's part i done -> its pass on pass0
+    hipEvent_t fork2 = nullptr;                     // EPA tier 2 done -> pass2
+    hipEvent_t join0 = nullptr, join2 = nullptr;    // pass0 / pass2 -> caller's stream
 };
 struct ForkKey {
     int dev;
@@ -189,24 +180,13 @@ int fork_state(hipStream_t s, Fork** out) {
     if (g_fork.size() >= kForkMax) return 0;
     Fork* f = new Fork();
     int least = 0, greatest = 0, prio = 0;
-    if (GJKEPA_FORK_PRIO != 0 && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
-        prio = GJKEPA_FORK_PRIO > 0 ? greatest : least;
-    for (int t = 0; t < GJKEPA_EPA_TIERS && e == hipSuccess; ++t) {
-        // a stream per fork point that forks (the first one only when shared)
-        const bool forks = ((GJKEPA_FORK_MASK >> t) & 1) && !(GJKEPA_LAST_PASS_MAIN && t == GJKEPA_EPA_TIERS - 1);
-        if (forks && (GJKEPA_FORK_STREAMS > 1 || !f->s2[0])) e = hipStreamCreateWithPriority(&f->s2[t], hipStreamNonBlocking, prio);
-        else if (forks) f->s2[t] = f->s2[0];
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&f->fork[t], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&f->join[t], hipEventDisableTiming);
-    }
-    for (int i = 0; i < 8 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&f->part[i], hipEventDisableTiming);
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess) prio = greatest;
+    // creation order (pass0, pass2, s3) decides which hardware queue each stream lands on
+    e = hipStreamCreateWithPriority(&f->pass0, hipStreamNonBlocking, prio);
+    if (e == hipSuccess) e = hipStreamCreateWithPriority(&f->pass2, hipStreamNonBlocking, prio);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->s3, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->fork3, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->join3, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&f->s4, hipStreamNonBlocking, prio);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->join4, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->fork23, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->join23, hipEventDisableTiming);
+    for (hipEvent_t* ev : {&f->fork3, &f->join3, &f->part[0], &f->part[1], &f->fork2, &f->join0, &f->join2})
+        if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
     if (e != hipSuccess) {
         delete f;
         return hip_fail(e, "overlap stream / events");
@@ -216,128 +196,32 @@ int fork_state(hipStream_t s, Fork** out) {
     return 0;
 }
 
+// stream `to` waits for what `from` holds so far
+int hop(hipEvent_t ev, hipStream_t from, hipStream_t to, const char* what) {
+    hipError_t e = hipEventRecord(ev, from);
+    if (e == hipSuccess) e = hipStreamWaitEvent(to, ev, 0);
+    return e == hipSuccess ? 0 : hip_fail(e, what);
+}
+
 // hull capacity (vertices) of EPA tier t (gjkepa_kernel.hip: epa_hull_cap)
 constexpr int epa_hull_cap(int t) {
     return t == 0 ? GJKEPA_E0_G * GJKEPA_E0_K : t == 1 ? GJKEPA_E1_G * GJKEPA_E1_K : t == 2 ? GJKEPA_E2_G * GJKEPA_E2_K
          : t == 3 ? GJKEPA_E3_G * GJKEPA_E3_K : t == 4 ? GJKEPA_E4_G * GJKEPA_E4_K : GJKEPA_E5_G * GJKEPA_E5_K;
 }
 
-// Fork points of an overlapped chain (bit t: a contact pass is forked after EPA tier t).  The pairs
-// EPA tier t finishes go to the contact pass of the first fork point p >= t (route code
-// GJKEPA_ROUTE_CT(p) + contact tier).  Default: after tier 0 (C2's hits), after tier 2 (C4 / C5's
-// 33-128-vertex hulls, with tier 1's few overflow pairs) and after the last tier (tiers 3-5): three
-// forks and five contact launches instead of one fork and up to two launches per tier, so the short
-// tail of a C2 chain carries three fewer near-empty launches.
-static_assert((GJKEPA_FORK_MASK >> (GJKEPA_EPA_TIERS - 1)) & 1, "the last EPA tier is a fork point");
-constexpr int fork_point(int t) {          // first fork point >= t
-    while (!((GJKEPA_FORK_MASK >> t) & 1)) ++t;
-    return t;
-}
-// contact tiers a fork point's pass needs: 1 when every hull of its EPA tiers fits contact tier 0
-constexpr int fork_contact_tiers(int p) {
-    int cap = 0;
-    for (int t = 0; t <= p; ++t)
-        if (fork_point(t) == p && epa_hull_cap(t) > cap) cap = epa_hull_cap(t);
-    return cap <= GJKEPA_C0_G * GJKEPA_C0_K ? 1 : GJKEPA_CONTACT_TIERS;
-}
-// EPA tier 0 in parts (GJKEPA_EPA0_PARTS; environment override for A/B): tier 0 runs over P
-// consecutive pair ranges, one launch each, and the contact pass of part i is forked as soon as part i
-// is done, so it runs beside the EPA of parts i+1.. instead of after all of tier 0 (C2's critical path
-// was GJK 0 -> EPA 0 -> the whole contact pass).  Which launch answers a pair never changes its record.
-#ifndef GJKEPA_EPA0_PARTS
-#define GJKEPA_EPA0_PARTS 2       // A/B r4 (C2, 2 rounds): 1 part 149.7, 2 parts 150.7, 4 parts 145.5, 8 parts 113.8 M/s
-#endif
-constexpr int kPartsMax = 4;
-int parts_env(const char* name, int dflt) {
-    const char* e = std::getenv(name);
-    const int v = e ? std::atoi(e) : dflt;
-    return v < 1 ? 1 : v > kPartsMax ? kPartsMax : v;
-}
-// the parts alternate between the caller's stream and a second internal stream (2), so a part's tail
-// overlaps the next part instead of idling the CUs it leaves (GJKEPA_EPA0_STREAMS, environment A/B)
-#ifndef GJKEPA_EPA0_STREAMS
-#define GJKEPA_EPA0_STREAMS 2     // A/B r4 (C2, 2 rounds, 2 parts): one stream 150.7, two streams 157.4 M/s
-#endif
-int epa0_streams() {
-    static const int p = [] {
-        const char* e = std::getenv("GJKEPA_EPA0_STREAMS");
-        const int v = e ? std::atoi(e) : GJKEPA_EPA0_STREAMS;
-        return v == 2 ? 2 : 1;
-    }();
-    return p;
-}
-// the contact passes of the odd parts on their own internal stream (2), so a part's pass starts when
-// its EPA part ends instead of queueing behind the previous part's pass (GJKEPA_PART_PASS_STREAMS)
-#ifndef GJKEPA_PART_PASS_STREAMS
-#define GJKEPA_PART_PASS_STREAMS 1
-#endif
-int part_pass_streams() {
-    static const int p = [] {
-        const char* e = std::getenv("GJKEPA_PART_PASS_STREAMS");
-        const int v = e ? std::atoi(e) : GJKEPA_PART_PASS_STREAMS;
-        return v == 2 ? 2 : 1;
-    }();
-    return p;
-}
-// share of the pair range in EPA tier 0's first part when it runs in two (per mille; environment
-// GJKEPA_EPA0_FIRST, A/B): the second part's contact pass is the chain's tail
-#ifndef GJKEPA_EPA0_FIRST
-#define GJKEPA_EPA0_FIRST 650      // A/B r4 (C2, 5 rounds): 500 157.6, 650 158.6, 700-750 158.5, 300 151.7 M/s
-#endif
-int epa0_first() {
-    static const int p = [] {
-        const char* e = std::getenv("GJKEPA_EPA0_FIRST");
-        const int v = e ? std::atoi(e) : GJKEPA_EPA0_FIRST;
-        return v < 100 ? 100 : v > 900 ? 900 : v;
-    }();
-    return p;
-}
-int epa0_parts() {
-    static const int p = parts_env("GJKEPA_EPA0_PARTS", GJKEPA_EPA0_PARTS);
-    return p;
-}
-// EPA tier 2 (hulls of 33-128 vertices: most of C5's pairs) in parts the same way (GJKEPA_EPA2_PARTS)
-#ifndef GJKEPA_EPA2_PARTS
-#define GJKEPA_EPA2_PARTS 1
-#endif
-int epa2_parts() {
-    static const int p = parts_env("GJKEPA_EPA2_PARTS", GJKEPA_EPA2_PARTS);
-    return p;
-}
-// launches of an overlapped chain: 2 GJK + the EPA tiers (tiers 0 and 2 in up to kPartsMax parts) +
-// each fork point's contact pass (once per part); every launch owns one workspace counter
-constexpr int overlap_launches() {
-    int n = GJKEPA_GJK_TIERS + GJKEPA_EPA_TIERS + 2 * (kPartsMax - 1);
-    for (int t = 0; t < GJKEPA_EPA_TIERS; ++t)
-        if ((GJKEPA_FORK_MASK >> t) & 1) n += fork_contact_tiers(t) * (t == 0 || t == 2 ? kPartsMax : 1);
-    return n;
-}
-static_assert(overlap_launches() + 1 <= GJKEPA_WS_COUNTERS, "workspace launch counters (+1: the fp32 redo launch)");
+// first fork point at or after EPA tier t in the overlapped chain
+constexpr int kForkPoint[GJKEPA_EPA_TIERS] = {0, 2, 2, 5, 5, 5};
+static_assert(epa_hull_cap(0) <= GJKEPA_C0_G * GJKEPA_C0_K, "the pass of fork point 0 needs contact tier 0 only");
+// share of the 64-pair chunks in EPA tier 0's first part (per mille): the second part's contact pass is
+// the chain's tail.  A/B r4 (C2, 5 rounds): 500 157.6, 650 158.6, 700-750 158.5, 300 151.7 M/s
+constexpr int64_t kEpa0First = 650;
+// Every launch of a chain but the reset owns one workspace counter.  The overlapped chain (enqueue's
+// list) has the most: the GJK tiers, EPA tier 0's two parts with a one-tier pass each, EPA tiers 1-5,
+// the two-tier passes of fork points 2 and 5, and the fp32 redo launch.
+constexpr int kChainCounters = GJKEPA_GJK_TIERS + 2 * 2 + (GJKEPA_EPA_TIERS - 1) + 2 * GJKEPA_CONTACT_TIERS + 1;
+static_assert(kChainCounters == 17 && kChainCounters <= GJKEPA_WS_COUNTERS, "workspace launch counters");
 static_assert(GJKEPA_ROUTE_REDO < GJKEPA_WS_TALLY && GJKEPA_ROUTE_REDO > GJKEPA_ROUTE_CT(GJKEPA_EPA_TIERS - 1) + 1,
               "redo route code");
-// The forked contact pass of EPA tier 0 (a dense launch) takes one workgroup per 64-pair chunk
-// instead of an occupancy-sized grid of looping workgroups: a workgroup leaves when its chunk is
-// done, so the EPA tiers launched beside the pass get wave slots as they free up instead of
-// queueing behind the whole pass (C2: the empty EPA tier 2 launch waited 657 us behind it).
-#ifndef GJKEPA_CONTACT_UNITS_GRID
-#define GJKEPA_CONTACT_UNITS_GRID 1
-#endif
-// EPA tiers 2 (hulls of 33-128 vertices) and 3 (129-256, first pass) serve disjoint pairs: with 2 they
-// run side by side, tier 3 on an internal stream forked after tier 1 and joined before tier 4, which
-// resumes both tiers' parked polytopes.  Tier 2's overflow then goes straight to tier 4 (a restart in
-// tier 3 would outgrow its 40-vertex polytope anyway; which tier answers never changes a record).
-// Environment override GJKEPA_E23_STREAMS for A/B.
-#ifndef GJKEPA_E23_STREAMS
-#define GJKEPA_E23_STREAMS 1       // A/B r5 (C4, 2 rounds): in sequence 39.51 / 39.41, side by side 38.54 / 38.63 M/s; C5 within 0.2%
-#endif
-int e23_streams() {
-    static const int p = [] {
-        const char* e = std::getenv("GJKEPA_E23_STREAMS");
-        const int v = e ? std::atoi(e) : GJKEPA_E23_STREAMS;
-        return v == 2 ? 2 : 1;
-    }();
-    return p;
-}
 
 // Park slots.  Only EPA tiers 2 and 3 park (hulls above EPA tier 1's capacity), so the park area a
 // batch can use is sized by its pairs with a hull above kParkMinHull vertices: gjkepa_workspace_bytes_for.
@@ -493,11 +377,7 @@ int enqueue(int32_t version, double tol_ff, int32_t vert_dtype, int32_t precisio
     a.verts = verts;
     a.hull_off = hull_off;
     a.hull_cnt = hull_cnt;
-    a.pairs = pairs;
-    a.n_pairs = n_pairs;
-    a.route = route;
     a.tally = tally;
-    a.out = out;
     a.num_cus = num_cus;
     a.park = park_slots > 0 ? (unsigned char*)workspace + ws_base(n_pairs) : nullptr;
     a.park_ctr = ctr + kWsParkWord;
@@ -507,48 +387,50 @@ int enqueue(int32_t version, double tol_ff, int32_t vert_dtype, int32_t precisio
     Fork* f = nullptr;
     int rc;
     if (n_pairs >= kOverlapMin && (rc = fork_state(s, &f))) return rc;
-    const bool overlap = f != nullptr;
-    // EPA tiers 2 and 3 side by side (not when a contact pass forks after tier 3)
-    const bool e23 = overlap && e23_streams() == 2 && !((GJKEPA_FORK_MASK >> 3) & 1);
-    const gjkepa_epa_args whole = a;                     // (a.pairs / route / out / n_pairs: a pair range below)
-    int64_t r_first = 0;                                 // the pair range `a` points at
-    auto range = [&](int64_t first, int64_t count) {     // point `a` at pairs [first, first + count)
-        a.pairs = whole.pairs + 2 * first;
-        a.route = whole.route + first;
-        a.out = (unsigned char*)whole.out + first * (precision == GJKEPA_PREC_F64 ? 128 : 64);
-        a.n_pairs = count;
-        r_first = first;
-    };
-    auto epa_tier = [&](int t, hipStream_t es) -> int {  // EPA tier t on stream es; polytope overflow -> next
-        a.route_code = GJKEPA_ROUTE_EPA0 + t;
-        // beside tier 3, tier 2's overflow goes to tier 4 (tier 3 is running: its tally is final at its start)
-        a.next_code = t == GJKEPA_EPA_TIERS - 1 ? -1 : GJKEPA_ROUTE_EPA0 + t + (e23 && t == 2 ? 2 : 1);
-        a.ct_base = overlap ? GJKEPA_ROUTE_CT(fork_point(t)) : GJKEPA_ROUTE_CT0;
+    struct Range { int64_t first, count; };
+    const Range all{0, n_pairs};
+    // one launch of an EPA / contact / redo kernel on the pairs of `r`: its route codes, claim and grid, the
+    // next workspace counter, then the guard over the finished block
+    auto launch_on = [&](const char* kind, int tier, int part, Range r, hipStream_t st, int route_code, int next_code,
+                         int claim, int grid, auto&& fn) {
+        a.pairs = pairs + 2 * r.first;
+        a.route = route + r.first;
+        a.out = (unsigned char*)out + r.first * (precision == GJKEPA_PREC_F64 ? 128 : 64);
+        a.n_pairs = r.count;
+        a.route_code = route_code;
+        a.next_code = next_code;
         a.ctr = ctr + launch++;
-        a.claim = t < GJKEPA_DENSE_EPA_TIERS ? 1 : kSparseClaim;
+        a.claim = claim;
+        a.grid = grid;
+        a.guard = gjkepa_guard_of(a);
+        return timed(kind, tier, part, route_code, r.first, r.count, st, [&] { return fn(st); });
+    };
+    // EPA tier t on stream es; polytope overflow goes to the next tier, finished pairs to the contact pass
+    // of their fork point (of the whole chain on one stream)
+    auto epa = [&](int t, int part, Range r, hipStream_t es) -> int {
+        constexpr int last = GJKEPA_EPA_TIERS - 1;
+        a.ct_base = f ? GJKEPA_ROUTE_CT(kForkPoint[t]) : GJKEPA_ROUTE_CT0;
         // the last tier (overflow of the 208-face polytope: rare) takes one workgroup per CU: its
         // one-wave-per-SIMD workgroups otherwise queue for dispatch behind a concurrent contact pass even
         // when the tier is empty (C5: an empty launch spanned 1.1 ms of the chain)
-        a.grid = t == GJKEPA_EPA_TIERS - 1 ? num_cus : 0;
-        a.guard = gjkepa_guard_of(a);
-        hipError_t er = timed("epa", t, 0, a.route_code, r_first, a.n_pairs, es,
-                              [&] { return gjkepa_launch_epa(t, vert_dtype, precision, a, es); });
+        const hipError_t er = launch_on("epa", t, part, r, es, GJKEPA_ROUTE_EPA0 + t, t == last ? -1 : GJKEPA_ROUTE_EPA0 + t + 1,
+                                        t < kDenseEpaTiers ? 1 : kSparseClaim, t == last ? num_cus : 0,
+                                        [&](hipStream_t st) { return gjkepa_launch_epa(t, vert_dtype, precision, a, st); });
         return er == hipSuccess ? 0 : hip_fail(er, "EPA tier launch");
     };
-    // contact features of the EPA results under route codes base + contact tier (tiers 0..ntiers-1).
-    // `single`: every launch claims single chunks.  A pass forked after one part of a parted tier must:
-    // the other parts are still adding to the route tally its sparse/dense choice (pick_claim) reads.
-    auto contact_tiers = [&](int base, int ntiers, hipStream_t cs, bool single, int part) -> int {
+    // contact features of the EPA results under route codes base + contact tier (tiers 0..ntiers-1) on
+    // stream cs.  `dense`: most pairs of the pass are in its tier 0, which claims single chunks.
+    auto contact_pass = [&](int base, int ntiers, int part, Range r, hipStream_t cs, bool dense) -> int {
         for (int t = 0; t < ntiers; ++t) {
-            a.route_code = base + t;
-            a.next_code = -1;
-            a.ctr = ctr + launch++;
-            a.claim = (single || (t == 0 && base <= GJKEPA_ROUTE_CT(0))) ? 1 : kSparseClaim;
-            // a forked dense pass (EPA tier 0's hits) takes one workgroup per chunk
-            a.grid = GJKEPA_CONTACT_UNITS_GRID && cs != s && a.claim == 1 ? GJKEPA_GRID_UNITS : 0;
-            a.guard = gjkepa_guard_of(a);
-            hipError_t er = timed("contact", t, part, a.route_code, r_first, a.n_pairs, cs,
-                                  [&] { return gjkepa_launch_contact(t, vert_dtype, precision, a, cs); });
+            const int claim = dense && t == 0 ? 1 : kSparseClaim;
+            // a dense launch on an internal stream takes one workgroup per 64-pair chunk instead of an
+            // occupancy-sized grid of looping workgroups: a workgroup leaves when its chunk is done, so the EPA
+            // tiers launched beside the pass get wave slots as they free up instead of queueing behind the
+            // whole pass (C2: the empty EPA tier 2 launch waited 657 us behind it)
+            const hipError_t er = launch_on("contact", t, part, r, cs, base + t, -1, claim,
+                                            cs != s && claim == 1 ? GJKEPA_GRID_UNITS : 0, [&](hipStream_t st) {
+                                                return gjkepa_launch_contact(t, vert_dtype, precision, a, st);
+                                            });
             if (er != hipSuccess) return hip_fail(er, "contact tier launch");
         }
         return 0;
@@ -557,106 +439,45 @@ int enqueue(int32_t version, double tol_ff, int32_t vert_dtype, int32_t precisio
     // contact pass has joined the caller's stream; an empty launch returns at once)
     auto redo = [&]() -> int {
         if (precision != GJKEPA_PREC_F32) return 0;
-        a.route_code = GJKEPA_ROUTE_REDO;
-        a.next_code = -1;
-        a.ctr = ctr + launch++;
-        a.claim = kSparseClaim;
-        a.grid = 0;
-        a.guard = gjkepa_guard_of(a);
-        hipError_t er = timed("redo", 0, 0, a.route_code, r_first, a.n_pairs, s,
-                              [&] { return gjkepa_launch_redo(vert_dtype, a, s); });
+        const hipError_t er = launch_on("redo", 0, 0, all, s, GJKEPA_ROUTE_REDO, -1, kSparseClaim, 0,
+                                        [&](hipStream_t st) { return gjkepa_launch_redo(vert_dtype, a, st); });
         return er == hipSuccess ? 0 : hip_fail(er, "fp32 redo launch");
     };
-    if (overlap) {
-        std::lock_guard<std::mutex> lk(f->mu);
-        constexpr int last = GJKEPA_EPA_TIERS - 1;
-        bool forked[GJKEPA_EPA_TIERS] = {};
-        // EPA tier t (a fork point that forks) in `parts` launches over consecutive pair ranges, alternately
-        // on the caller's stream and an internal one, each range's contact pass forked when it is done
-        bool used4 = false;
-        auto parted = [&](int t, int parts) -> int {
-            const int64_t chunks = (n_pairs + 63) / 64;
-            const bool two = epa0_streams() == 2;
-            if (two && ((e = hipEventRecord(f->fork3, s)) != hipSuccess || (e = hipStreamWaitEvent(f->s3, f->fork3, 0)) != hipSuccess))
-                return hip_fail(e, "EPA part stream fork");
-            for (int i = 0; i < parts; ++i) {
-                int64_t c0 = chunks * i / parts, c1 = chunks * (i + 1) / parts;
-                if (t == 0 && parts == 2) {                  // uneven halves (GJKEPA_EPA0_FIRST)
-                    const int64_t cut = chunks * epa0_first() / 1000;
-                    c0 = i == 0 ? 0 : cut;
-                    c1 = i == 0 ? cut : chunks;
-                }
-                const int64_t first = c0 * 64, count = (c1 * 64 < n_pairs ? c1 * 64 : n_pairs) - first;
-                if (count <= 0) continue;
-                range(first, count);
-                hipStream_t ps = two && (i & 1) ? f->s3 : s;
-                a.route_code = GJKEPA_ROUTE_EPA0 + t;
-                a.next_code = GJKEPA_ROUTE_EPA0 + t + 1;
-                a.ct_base = GJKEPA_ROUTE_CT(fork_point(t));
-                a.ctr = ctr + launch++;
-                a.claim = t < GJKEPA_DENSE_EPA_TIERS ? 1 : kSparseClaim;
-                a.grid = 0;
-                a.guard = gjkepa_guard_of(a);
-                if ((e = timed("epa", t, i, a.route_code, first, count, ps,
-                               [&] { return gjkepa_launch_epa(t, vert_dtype, precision, a, ps); })) != hipSuccess)
-                    return hip_fail(e, "EPA tier launch");
-                hipEvent_t pe = f->part[(t == 0 ? 0 : kPartsMax) + i];
-                hipStream_t cs = part_pass_streams() == 2 && (i & 1) ? f->s4 : f->s2[t];
-                if ((e = hipEventRecord(pe, ps)) != hipSuccess || (e = hipStreamWaitEvent(cs, pe, 0)) != hipSuccess)
-                    return hip_fail(e, "contact pass fork");
-                if ((rc = contact_tiers(GJKEPA_ROUTE_CT(t), fork_contact_tiers(t), cs, true, i))) return rc;
-                if (cs == f->s4) used4 = true;
-            }
-            if (two && ((e = hipEventRecord(f->join3, f->s3)) != hipSuccess || (e = hipStreamWaitEvent(s, f->join3, 0)) != hipSuccess))
-                return hip_fail(e, "EPA part stream join");
-            a = whole;
-            r_first = 0;
-            forked[t] = true;
-            return 0;
-        };
-        for (int t = 0; t < GJKEPA_EPA_TIERS; ++t) {
-            const bool forks = ((GJKEPA_FORK_MASK >> t) & 1) && !(GJKEPA_LAST_PASS_MAIN && t == last);
-            if (e23 && t == 2) {
-                // tier 3 on s3, forked here (after tier 1) and joined below before tier 4
-                if ((e = hipEventRecord(f->fork23, s)) != hipSuccess || (e = hipStreamWaitEvent(f->s3, f->fork23, 0)) != hipSuccess)
-                    return hip_fail(e, "EPA tier 3 stream fork");
-                if ((rc = epa_tier(3, f->s3))) return rc;
-                if ((e = hipEventRecord(f->join23, f->s3)) != hipSuccess) return hip_fail(e, "EPA tier 3 stream join");
-            }
-            if (e23 && t == 3) continue;                     // launched beside tier 2
-            if (e23 && t == 4 && (e = hipStreamWaitEvent(s, f->join23, 0)) != hipSuccess)
-                return hip_fail(e, "EPA tier 3 stream join");
-            const int np = !forks ? 1 : t == 0 ? epa0_parts() : t == 2 && !e23 ? epa2_parts() : 1;
-            if (np > 1) {
-                if ((rc = parted(t, np))) return rc;
-                continue;
-            }
-            if ((rc = epa_tier(t, s))) return rc;
-            if (!((GJKEPA_FORK_MASK >> t) & 1)) continue;
-            if (GJKEPA_LAST_PASS_MAIN && t == last) {
-                if ((rc = contact_tiers(GJKEPA_ROUTE_CT(t), fork_contact_tiers(t), s, false, 0))) return rc;
-                continue;
-            }
-            if ((e = hipEventRecord(f->fork[t], s)) != hipSuccess || (e = hipStreamWaitEvent(f->s2[t], f->fork[t], 0)) != hipSuccess)
-                return hip_fail(e, "contact pass fork");
-            if ((rc = contact_tiers(GJKEPA_ROUTE_CT(t), fork_contact_tiers(t), f->s2[t], false, 0))) return rc;
-            forked[t] = true;
-        }
-        for (int t = 0; t < GJKEPA_EPA_TIERS; ++t) {      // join every internal stream used (last one per stream)
-            if (!forked[t]) continue;
-            bool later = false;
-            for (int u = t + 1; u < GJKEPA_EPA_TIERS; ++u) later = later || (forked[u] && f->s2[u] == f->s2[t]);
-            if (later) continue;
-            if ((e = hipEventRecord(f->join[t], f->s2[t])) != hipSuccess || (e = hipStreamWaitEvent(s, f->join[t], 0)) != hipSuccess)
-                return hip_fail(e, "contact pass join");
-        }
-        if (used4 && ((e = hipEventRecord(f->join4, f->s4)) != hipSuccess || (e = hipStreamWaitEvent(s, f->join4, 0)) != hipSuccess))
-            return hip_fail(e, "contact pass join");
+    if (!f) {                                            // the single-stream chain
+        for (int t = 0; t < GJKEPA_EPA_TIERS; ++t)
+            if ((rc = epa(t, 0, all, s))) return rc;
+        if ((rc = contact_pass(GJKEPA_ROUTE_CT0, GJKEPA_CONTACT_TIERS, 0, all, s, true))) return rc;
         return redo();
     }
-    for (int t = 0; t < GJKEPA_EPA_TIERS; ++t)
-        if ((rc = epa_tier(t, s))) return rc;
-    if ((rc = contact_tiers(GJKEPA_ROUTE_CT0, GJKEPA_CONTACT_TIERS, s, false, 0))) return rc;
+    // The overlapped chain.  Streams: s the caller's, f->s3 for EPA tier 0's second part, f->pass0 and
+    // f->pass2 for the contact passes of fork points 0 and 2.
+    std::lock_guard<std::mutex> lk(f->mu);
+    // EPA tier 0 in two parts, [0, cut) chunks on s and the rest on s3, each followed by its contact pass on
+    // pass0.  Both passes claim single chunks whatever the route tally says: the other part is still
+    // adding to the tally a sparse launch's sparse / dense choice (pick_claim) would read.
+    const int64_t cut = (n_pairs + 63) / 64 * kEpa0First / 1000 * 64;
+    const Range part[2] = {{0, cut}, {cut, n_pairs - cut}};
+    const hipStream_t part_stream[2] = {s, f->s3};
+    if ((rc = hop(f->fork3, s, f->s3, "EPA part stream fork"))) return rc;
+    for (int i = 0; i < 2; ++i) {
+        if (part[i].count <= 0) continue;
+        if ((rc = epa(0, i, part[i], part_stream[i]))) return rc;
+        if ((rc = hop(f->part[i], part_stream[i], f->pass0, "contact pass fork"))) return rc;
+        if ((rc = contact_pass(GJKEPA_ROUTE_CT(0), 1, i, part[i], f->pass0, true))) return rc;
+    }
+    if ((rc = hop(f->join3, f->s3, s, "EPA part stream join"))) return rc;
+    // EPA tiers 1 and 2 on s, then their contact pass on pass2 beside the tiers that follow
+    if ((rc = epa(1, 0, all, s))) return rc;
+    if ((rc = epa(2, 0, all, s))) return rc;
+    if ((rc = hop(f->fork2, s, f->pass2, "contact pass fork"))) return rc;
+    if ((rc = contact_pass(GJKEPA_ROUTE_CT(2), GJKEPA_CONTACT_TIERS, 0, all, f->pass2, false))) return rc;
+    // EPA tiers 3-5 and their contact pass on s
+    for (int t = 3; t < GJKEPA_EPA_TIERS; ++t)
+        if ((rc = epa(t, 0, all, s))) return rc;
+    if ((rc = contact_pass(GJKEPA_ROUTE_CT(GJKEPA_EPA_TIERS - 1), GJKEPA_CONTACT_TIERS, 0, all, s, false))) return rc;
+    // both pass streams join s
+    if ((rc = hop(f->join0, f->pass0, s, "contact pass join"))) return rc;
+    if ((rc = hop(f->join2, f->pass2, s, "contact pass join"))) return rc;
     return redo();
 }
 

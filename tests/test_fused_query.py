@@ -1,5 +1,5 @@
 """The one-kernel query path (query_kernel: GJK, EPA and the contact features in one wave per pair)
-that serves batches of up to GJKEPA_FUSED_MAX (64) pairs, e.g. combined single-pair gjkepa_query
+that serves batches of up to kFusedMax (64) pairs, e.g. combined single-pair gjkepa_query
 calls.  It runs the tier kernels' device functions with the largest tier's capacities, so every
 record must equal the tier chain's and the oracle's byte for byte: each golden fixture and the
 branch-coverage fixture (the reference's rare paths, incl. DEGENERATE, EPA_MAXITER, BAD_VERSION,
