@@ -233,4 +233,76 @@ DS_HD Result dist_gjk(Simplex& s, double max_distance, Sup&& sup, Pt&& pt, Sqrt&
     return r;
 }
 
+// dist_gjk with a resume entry, for a caller that runs the iteration again after every Minkowski point
+// has moved by the same vector (cast_advance.h).  carried = false: dist_gjk's start, pt(0, 0).
+// carried = true: s holds n <= 3 codes of an earlier run; the points are rebuilt from the codes with
+// pt, the simplex is reduced once from scratch (its closest point has moved with the points; vertex 0
+// is reduce's starting candidate, so every feature is offered), and the iteration goes on from there.
+// Same tests and exits as dist_gjk, with two differences in what comes back: iters counts the support
+// evaluations of this run only, and after the exit `reduce brought v no closer` v is the point the
+// last support was taken along, so that lower = min over A - B of x.v / |v| holds for the v returned
+// (the simplex and its weights are the reduced ones, as in dist_gjk).
+template <typename Sup, typename Pt, typename Sqrt>
+DS_HD Result dist_gjk_from(Simplex& s, bool carried, double max_distance, Sup&& sup, Pt&& pt, Sqrt&& sqrt_) {
+    Result r;
+    r.outcome = DIST_MAXITER;
+    r.iters = 0;
+    r.lower = 0.0;
+    if (!carried) {
+        s.n = 1;
+        s.code[0] = 0u;
+#pragma unroll
+        for (int k = 1; k < 4; ++k) s.code[k] = kDistNoCode;
+    }
+    double scale2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        s.y[k] = mk(0.0, 0.0, 0.0);
+        s.lam[k] = k == 0 ? 1.0 : 0.0;
+        if (k < 3 && k < s.n) {
+            s.y[k] = pt((int)(s.code[k] & 0xffffu), (int)(s.code[k] >> 16));
+            const double ww = dot(s.y[k], s.y[k]);
+            scale2 = ww > scale2 ? ww : scale2;
+        }
+    }
+    bool fresh = s.n > 1;                   // a carried simplex: reduce before the first support
+    D3 v = s.y[0];
+    double vv = fresh ? 1.0e300 : dot(v, v);
+    for (;;) {
+        if (!fresh) {
+            if (!(vv > kDistZero2 * scale2)) { r.outcome = DIST_OVERLAP; break; }
+            if (r.iters >= kDistMaxIter) break;
+            r.iters += 1;
+            int ia, ib;
+            sup(neg(v), ia, ib);
+            const D3 w = pt(ia, ib);
+            const double vw = dot(v, w);
+            r.lower = vw > 0.0 ? vw / sqrt_(vv) : 0.0;
+            if (r.lower > max_distance) { r.outcome = DIST_FAR; break; }
+            if (vv - vw <= kDistEps * vv) { r.outcome = DIST_SEPARATED; break; }
+            const uint32_t code = (uint32_t)ia | ((uint32_t)ib << 16);
+            bool seen = false;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) seen = seen || (k < s.n && s.code[k] == code);
+            if (seen) { r.outcome = DIST_SEPARATED; break; }
+#pragma unroll
+            for (int k = 1; k < 4; ++k)
+                if (s.n == k) { s.y[k] = w; s.code[k] = code; s.lam[k] = 0.0; }
+            s.n += 1;
+            const double ww = dot(w, w);
+            scale2 = ww > scale2 ? ww : scale2;
+        }
+        fresh = false;
+        double bvv;
+        if (reduce(s, scale2, bvv)) { r.outcome = DIST_OVERLAP; break; }
+        const D3 nv = closest(s);
+        const double nvv = dot(nv, nv);
+        if (!(nvv < vv)) { r.outcome = DIST_SEPARATED; break; }
+        v = nv;
+        vv = nvv;
+    }
+    r.v = v;
+    return r;
+}
+
 }  // namespace gkd

@@ -8,7 +8,8 @@
 // takes 64-pair chunks (or runs of 16) from its own counter.  gjkepa_hull_batch(_device) follow the
 // same pattern for the batched convex-hull kernels (two tiers over one cloud list), and
 // gjkepa_distance_batch(_device) for the separation-distance tiers (a counter reset and three launches on
-// the caller's stream, counters in a workspace of their own).
+// the caller's stream, counters in a workspace of their own), and gjkepa_cast_batch(_device) for the
+// linear-cast tiers (the same chain shape).
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -97,7 +98,8 @@ struct DeviceState {
     DevBuf b_pairs, b_count, b_ws;                          // gjkepa_broadphase staging
     DevBuf c_idx, c_hits, c_ws, c_n;                        // gjkepa_collide staging
     DevBuf q_blk, q_ws;                                     // combined gjkepa_query batches
-    DevBuf d_rec, d_out, d_ws;                              // gjkepa_distance_batch staging
+    DevBuf d_rec, d_out, d_ws;                              // gjkepa_distance_batch / gjkepa_cast_batch staging
+    DevBuf d_motion;                                        // gjkepa_cast_batch staging
     HostBuf q_host;
 };
 
@@ -772,6 +774,134 @@ int gjkepa_distance_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_
                           max_distance, d->d_out.p, d->d_ws.p, (int64_t)d->d_ws.cap, s, d->num_cus);
     if (rc) return rc;
     if ((e = hipMemcpyAsync(out, d->d_out.p, (size_t)n_pairs * sizeof(gjkepa_distance_f64), hipMemcpyDeviceToHost, s)) != hipSuccess)
+        return hip_fail(e, "hipMemcpyAsync D2H");
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    return 0;
+}
+
+// ---- linear cast ---------------------------------------------------------------------------------
+int gjkepa_cast_record_bytes(void) { return (int)sizeof(gjkepa_cast_f64); }
+
+int64_t gjkepa_cast_workspace_bytes(int64_t n_pairs) {
+    if (n_pairs < 0) return GJKEPA_E_ARG;
+    return GJKEPA_CAST_WS_BYTES;       // the tier launches' chunk counters: independent of the batch size
+}
+
+}  // extern "C"
+
+namespace {
+static_assert(sizeof(gjkepa_cast_f64) == 128, "gjkepa_cast_f64 layout (gjkepa.py CAST64)");
+static_assert(offsetof(gjkepa_cast_f64, iters) == offsetof(gjkepa_distance_f64, iters) &&
+              offsetof(gjkepa_cast_f64, steps) == offsetof(gjkepa_distance_f64, pad), "the cast record is packed as the distance record");
+static_assert(GJKEPA_GJK_TIERS * sizeof(uint32_t) <= GJKEPA_CAST_WS_BYTES, "one counter per cast tier");
+// the checks the device and the host entry share, before any device work
+int cast_args_ok(int32_t vert_dtype, int64_t n_pairs, const void* records, int32_t records_precision, double tolerance) {
+    if (n_pairs < 0 || (vert_dtype != GJKEPA_DTYPE_F32 && vert_dtype != GJKEPA_DTYPE_F64))
+        return fail(GJKEPA_E_ARG, "bad n_pairs/dtype");
+    if (records && records_precision != GJKEPA_PREC_F32 && records_precision != GJKEPA_PREC_F64)
+        return fail(GJKEPA_E_ARG, "bad records_precision");
+    if (!(tolerance > 0.0) || !(tolerance <= 1.7976931348623157e308))
+        return fail(GJKEPA_E_ARG, "tolerance is NaN, infinite, zero or negative");
+    if (n_pairs > INT32_MAX) return fail(GJKEPA_E_ARG, "n_pairs above 2^31-1");
+    return 0;
+}
+// the chain: counter reset, then one launch per tier, all on the caller's stream
+int cast_enqueue(int32_t vert_dtype, const void* verts, const int64_t* hull_off, const int32_t* hull_cnt,
+                 const int32_t* pairs, int64_t n_pairs, const double* motion, double tolerance, const void* records,
+                 int32_t records_precision, void* out, void* workspace, int64_t ws_bytes, hipStream_t s, int num_cus) {
+    if (n_pairs == 0) return 0;
+    if (ws_bytes < GJKEPA_CAST_WS_BYTES) return fail(GJKEPA_E_WORKSPACE, "workspace too small");
+    uint32_t* ctr = (uint32_t*)workspace;
+    hipError_t e;
+    if ((e = gjkepa_launch_ws_reset(ctr, GJKEPA_CAST_WS_BYTES / 4, s)) != hipSuccess)
+        return hip_fail(e, "cast workspace reset");
+    gjkepa_cast_args a{};
+    a.verts = verts;
+    a.hull_off = hull_off;
+    a.hull_cnt = hull_cnt;
+    a.pairs = pairs;
+    a.n_pairs = n_pairs;
+    a.records = (const unsigned char*)records;
+    a.rec_stride = records_precision == GJKEPA_PREC_F64 ? (int)sizeof(gjkepa_contact_f64) : (int)sizeof(gjkepa_contact_f32);
+    a.rec_hit_off = records_precision == GJKEPA_PREC_F64 ? (int)offsetof(gjkepa_contact_f64, collision)
+                                                         : (int)offsetof(gjkepa_contact_f32, collision);
+    a.motion = motion;
+    a.tolerance = tolerance;
+    a.out = out;
+    a.num_cus = num_cus;
+    for (int t = 0; t < GJKEPA_GJK_TIERS; ++t) {
+        a.ctr = ctr + t;
+        if ((e = gjkepa_launch_cast(t, vert_dtype, a, s)) != hipSuccess) return hip_fail(e, "cast tier launch");
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int gjkepa_cast_batch_device(int32_t vert_dtype, const void* verts, const int64_t* hull_off,
+                             const int32_t* hull_cnt, const int32_t* pairs, int64_t n_pairs,
+                             const double* motion, double tolerance, const void* records, int32_t records_precision,
+                             void* out, void* workspace, int64_t workspace_bytes, void* stream) {
+    const gjkepa_internal::Range range_("gjkepa_cast_batch_device (chain enqueue)");
+    int rc = cast_args_ok(vert_dtype, n_pairs, records, records_precision, tolerance);
+    if (rc) return rc;
+    if (n_pairs > 0 && (!verts || !hull_off || !hull_cnt || !pairs || !motion || !out || !workspace))
+        return fail(GJKEPA_E_ARG, "null pointer");
+    if (n_pairs == 0) return 0;
+    if (workspace_bytes < GJKEPA_CAST_WS_BYTES) return fail(GJKEPA_E_WORKSPACE, "workspace too small");
+    return cast_enqueue(vert_dtype, verts, hull_off, hull_cnt, pairs, n_pairs, motion, tolerance, records,
+                        records_precision, out, workspace, workspace_bytes, (hipStream_t)stream, num_cus_current());
+}
+
+int gjkepa_cast_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
+                      const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                      const int32_t* pairs, int64_t n_pairs, const double* motion, double tolerance,
+                      const void* records, int32_t records_precision, void* out, int32_t device) {
+    const gjkepa_internal::Range range_("gjkepa_cast_batch (H2D, chain, D2H)");
+    if (n_hulls < 0 || n_vert_scalars < 0) return fail(GJKEPA_E_ARG, "bad sizes");
+    int rc = cast_args_ok(vert_dtype, n_pairs, records, records_precision, tolerance);
+    if (rc) return rc;
+    if (n_pairs == 0) return 0;
+    if (!verts || !hull_off || !hull_cnt || !pairs || !motion || !out) return fail(GJKEPA_E_ARG, "null pointer");
+    // host-side validation of the index structure (device code trusts it), as gjkepa_batch
+    for (int64_t k = 0; k < 2 * n_pairs; ++k)
+        if (pairs[k] < 0 || pairs[k] >= n_hulls) return fail(GJKEPA_E_ARG, "pair references a missing hull");
+    for (int64_t h = 0; h < n_hulls; ++h) {
+        int64_t c = hull_cnt[h];
+        if (c >= 1 && (hull_off[h] < 0 || hull_off[h] + 3 * c > n_vert_scalars))
+            return fail(GJKEPA_E_ARG, "hull outside the vertex pool");
+    }
+    DeviceState* d = device_state(device, &rc);
+    if (!d) return rc;
+    std::lock_guard<std::mutex> g(d->mu);
+    if ((rc = init_device(d, device))) return rc;
+    hipError_t e;
+    const size_t esz = vert_dtype == GJKEPA_DTYPE_F32 ? 4 : 8;
+    const size_t rec = records ? (size_t)gjkepa_record_bytes(records_precision) : 0;
+    if ((e = d->verts.ensure((size_t)n_vert_scalars * esz)) != hipSuccess ||
+        (e = d->off.ensure((size_t)n_hulls * 8)) != hipSuccess ||
+        (e = d->cnt.ensure((size_t)n_hulls * 4)) != hipSuccess ||
+        (e = d->pairs.ensure((size_t)n_pairs * 8)) != hipSuccess ||
+        (e = d->d_motion.ensure((size_t)n_pairs * 24)) != hipSuccess ||
+        (e = d->d_rec.ensure((size_t)n_pairs * rec)) != hipSuccess ||
+        (e = d->d_out.ensure((size_t)n_pairs * sizeof(gjkepa_cast_f64))) != hipSuccess ||
+        (e = d->d_ws.ensure((size_t)GJKEPA_CAST_WS_BYTES)) != hipSuccess)
+        return hip_fail(e, "hipMalloc");
+    hipStream_t s = d->stream;
+    if ((e = hipMemcpyAsync(d->verts.p, verts, (size_t)n_vert_scalars * esz, hipMemcpyHostToDevice, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(d->off.p, hull_off, (size_t)n_hulls * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(d->cnt.p, hull_cnt, (size_t)n_hulls * 4, hipMemcpyHostToDevice, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(d->pairs.p, pairs, (size_t)n_pairs * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(d->d_motion.p, motion, (size_t)n_pairs * 24, hipMemcpyHostToDevice, s)) != hipSuccess ||
+        (records && (e = hipMemcpyAsync(d->d_rec.p, records, (size_t)n_pairs * rec, hipMemcpyHostToDevice, s)) != hipSuccess))
+        return hip_fail(e, "hipMemcpyAsync H2D");
+    rc = cast_enqueue(vert_dtype, d->verts.p, (const int64_t*)d->off.p, (const int32_t*)d->cnt.p,
+                      (const int32_t*)d->pairs.p, n_pairs, (const double*)d->d_motion.p, tolerance,
+                      records ? d->d_rec.p : nullptr, records_precision, d->d_out.p, d->d_ws.p, (int64_t)d->d_ws.cap, s,
+                      d->num_cus);
+    if (rc) return rc;
+    if ((e = hipMemcpyAsync(out, d->d_out.p, (size_t)n_pairs * sizeof(gjkepa_cast_f64), hipMemcpyDeviceToHost, s)) != hipSuccess)
         return hip_fail(e, "hipMemcpyAsync D2H");
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     return 0;

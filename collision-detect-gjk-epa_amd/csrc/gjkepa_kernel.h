@@ -388,8 +388,41 @@ struct gjkepa_dist_args {
     void* out;                      // gjkepa_distance_f64 records
     int grid;                       // <= 0: occupancy x CUs
     int num_cus;
+    static constexpr int kSkipFlag = GJKEPA_DIST_HIT;   // flag of a pair the contact records call a collision
 };
 hipError_t gjkepa_launch_dist(int tier, int vert_dtype, const gjkepa_dist_args& a, hipStream_t s);
+
+// ---- linear cast (gjkepa_cast_batch_device): conservative advancement over the distance GJK
+// (cast_advance.h), on the distance tiers' shapes, pair schedule (for_each_dist_pair reads the fields
+// the two argument blocks share by name) and workspace layout.
+#ifndef GJKEPA_K0_MINW
+#define GJKEPA_K0_MINW 2        // waves per SIMD of the cast tiers
+#endif
+#ifndef GJKEPA_K1_MINW
+#define GJKEPA_K1_MINW 2
+#endif
+#ifndef GJKEPA_K2_MINW
+#define GJKEPA_K2_MINW 2
+#endif
+#define GJKEPA_CAST_WS_BYTES GJKEPA_DIST_WS_BYTES
+struct gjkepa_cast_args {
+    const void* verts;
+    const int64_t* hull_off;
+    const int32_t* hull_cnt;
+    const int32_t* pairs;
+    int64_t n_pairs;
+    const unsigned char* records;   // optional contact records of the same pair list (nullptr: none)
+    int rec_stride;
+    int rec_hit_off;
+    const double* motion;           // 3 doubles per pair: hull B's displacement relative to hull A
+    double tolerance;               // the cast stops within this distance (finite, > 0)
+    uint32_t* ctr;                  // this launch's chunk counter (zero at launch)
+    void* out;                      // gjkepa_cast_f64 records
+    int grid;                       // <= 0: occupancy x CUs
+    int num_cus;
+    static constexpr int kSkipFlag = GJKEPA_CAST_SKIPPED;
+};
+hipError_t gjkepa_launch_cast(int tier, int vert_dtype, const gjkepa_cast_args& a, hipStream_t s);
 
 hipError_t gjkepa_launch_gjk(int tier, int vert_dtype, int precision, const gjkepa_gjk_args& a, hipStream_t s);
 hipError_t gjkepa_launch_epa(int tier, int vert_dtype, int precision, const gjkepa_epa_args& a, hipStream_t s);

@@ -41,6 +41,9 @@
 #if GK_IN(12)
 #include "dist_simplex.h"       // the distance GJK's simplex arithmetic (host and device)
 #endif
+#if GK_IN(13)
+#include "cast_advance.h"       // the linear cast: conservative advancement over the distance GJK
+#endif
 
 namespace gk {
 
@@ -2869,12 +2872,12 @@ __global__ __launch_bounds__(64) void ws_reset_kernel(uint32_t* ws, int n32, uin
 }
 #endif  // GK_IN(0)
 
-#if GK_IN(12)
+#if GK_IN(12) || GK_IN(13)
 // ---------------------------------------------------------------- separation distance
 // gjkepa_distance_f64: 13 doubles (distance, point_a, point_b, normal, lambda), code[3], the four
-// int8 fields, iters, pad.  Its 16 8-byte words are stored from registers, word j by group lane j % G.
+// int8 fields, iters, pad (the cast record: steps).  Its 16 8-byte words are stored from registers, word j by group lane j % G.
 template <int G> DEV void store_dist(void* out, int64_t pair, int gl, const double* o13, const uint32_t* code, int n,
-                                     int status, int flags, uint32_t iters) {
+                                     int status, int flags, uint32_t iters, uint32_t steps = 0u) {
     const uint32_t tail = (uint32_t)(n & 0xff) | ((uint32_t)(status & 0xff) << 8) | ((uint32_t)(flags & 0xff) << 16);
 #pragma unroll
     for (int j0 = 0; j0 < 16; j0 += G) {
@@ -2886,7 +2889,7 @@ template <int G> DEV void store_dist(void* out, int64_t pair, int gl, const doub
         uint64_t word = __builtin_bit_cast(uint64_t, v);
         if (j == 13) word = (uint64_t)code[0] | ((uint64_t)code[1] << 32);
         if (j == 14) word = (uint64_t)code[2] | ((uint64_t)tail << 32);
-        if (j == 15) word = (uint64_t)iters;
+        if (j == 15) word = (uint64_t)iters | ((uint64_t)steps << 32);
         reinterpret_cast<uint64_t*>(out)[pair * 16 + j] = word;
     }
 }
@@ -2908,9 +2911,10 @@ DEV void store_dist_empty(void* out, int64_t pair, int status, int flags) {
 // a hit of this tier's bracket), and only the pairs left go to the groups.  After a batch most
 // candidate pairs are hits (C2: 73%): handed to the groups they would leave three groups in four of
 // every round idle (measured, 2^20 C2 pairs: 1.99 ms with every pair handed out, 1.40 ms with this
-// filter; 2^22 C4 pairs 16.1 -> 10.5 ms).
-template <int G, int CAP, int TIER, typename F>
-DEV void for_each_dist_pair(const Grp<G>& grp, const gjkepa_dist_args& a, F&& f) {
+// filter; 2^22 C4 pairs 16.1 -> 10.5 ms).  ARGS: gjkepa_dist_args, or the cast's gjkepa_cast_args (the
+// same fields and its own skip flag).
+template <int G, int CAP, int TIER, typename ARGS, typename F>
+DEV void for_each_dist_pair(const Grp<G>& grp, const ARGS& a, F&& f) {
     constexpr int LO = TIER == 0 ? 0 : TIER == 1 ? GJKEPA_G0_G * GJKEPA_G0_K : GJKEPA_G1_G * GJKEPA_G1_K;
     static_assert(LO < CAP, "tier brackets ascend");
     const Units U(a.n_pairs, tail_unit<G, (64 / G > 8 ? 64 / G : 8)>(a.n_pairs));
@@ -2931,7 +2935,7 @@ DEV void for_each_dist_pair(const Grp<G>& grp, const gjkepa_dist_args& a, F&& f)
                 if (TIER == 0) store_dist_empty(a.out, p, GJKEPA_STATUS_BAD_INPUT, 0);
             } else if (nmax > LO && nmax <= CAP) {
                 if (a.records && a.records[p * (int64_t)a.rec_stride + a.rec_hit_off] != 0)
-                    store_dist_empty(a.out, p, GJKEPA_STATUS_OK, GJKEPA_DIST_HIT);
+                    store_dist_empty(a.out, p, GJKEPA_STATUS_OK, ARGS::kSkipFlag);
                 else
                     take = true;
             }
@@ -2941,6 +2945,7 @@ DEV void for_each_dist_pair(const Grp<G>& grp, const gjkepa_dist_args& a, F&& f)
     }
 }
 
+#if GK_IN(12)
 // Distance kernel of tier TIER (group shape G x K as GJK tier TIER): every pair of the list whose
 // larger hull has LO < n <= G K vertices (tier 0 also answers the bad counts).  The simplex logic
 // (dist_simplex.h) is group-uniform like gjk_phase's; the support scans are the contact path's.
@@ -3005,6 +3010,58 @@ __global__ __launch_bounds__(64, MINW) void dist_kernel(const gjkepa_dist_args a
     for_each_dist_pair<G, G * K, TIER>(grp, a, body);
 }
 #endif  // GK_IN(12)
+#endif  // GK_IN(12) || GK_IN(13)
+
+#if GK_IN(13)
+// ---------------------------------------------------------------- linear cast
+// Cast kernel of tier TIER: the distance tiers' shapes, schedule and record packing (the word that is
+// the distance record's pad holds the step count), one group per pair.  cast_advance.h runs the distance
+// GJK once per advancement step, group-uniform; the simplex points are rebuilt from their codes at each
+// step, so the group keeps one simplex, the motion and the step's offset t d.
+static_assert(gkd::kCastFlagImpact == GJKEPA_CAST_IMPACT && gkd::kCastFlagStart == GJKEPA_CAST_START &&
+              gkd::kCastStatusMaxIter == GJKEPA_STATUS_CAST_MAXITER, "cast_advance.h against gjkepa.h");
+template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
+__global__ __launch_bounds__(64, MINW) void cast_kernel(const gjkepa_cast_args a) {
+    using T = double;
+    using L_t = Lds<T, TIn, G, K, 0, 0>;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const Grp<G> grp;
+    L_t& L = *reinterpret_cast<L_t*>(smem + lds_stride<L_t, G>() * (grp.lane / G));
+    const int gl = grp.gl;
+    const TIn* verts = (const TIn*)a.verts;
+    auto body = [&](int64_t pair, const PairMeta& pm) {      // a pair of this tier with valid counts, not skipped
+        Ctx<T, TIn, G, K, 0, 0, LH> c{L, grp};
+        double o13[13];
+#pragma unroll
+        for (int i = 0; i < 13; ++i) o13[i] = 0.0;
+        uint32_t code[3] = {gkd::kDistNoCode, gkd::kDistNoCode, gkd::kDistNoCode};
+        c.na = grp.uni(pm.na);
+        c.nb = grp.uni(pm.nb);
+        const gkd::D3 d = gkd::mk(a.motion[3 * pair], a.motion[3 * pair + 1], a.motion[3 * pair + 2]);
+        const bool bad_motion = !(isfinite(d.x) && isfinite(d.y) && isfinite(d.z));
+        if (load_hulls(c, verts + pm.oa, verts + pm.ob) || bad_motion) {
+            store_dist<G>(a.out, pair, gl, o13, code, 0, GJKEPA_STATUS_BAD_INPUT, 0, 0u);
+            __builtin_amdgcn_wave_barrier();
+            return;
+        }
+        gkd::Simplex s;
+        const gkd::CastResult r = gkd::cast_advance(
+            s, d, a.tolerance,
+            [&](gkd::D3 dir, int& ia, int& ib) { support_idx(c, vmk<T>(dir.x, dir.y, dir.z), ia, ib); },
+            [&](int ia, int ib) { const V3<T> p = vsub(c.A(ia), c.B(ib)); return gkd::mk(p.x, p.y, p.z); },
+            [](double x) { return tsqrt(x); });
+        int n, status, flags;
+        gkd::cast_record(
+            r, s, d, [&](int i) { const V3<T> p = c.A(i); return gkd::mk(p.x, p.y, p.z); },
+            [&](int i) { const V3<T> p = c.B(i); return gkd::mk(p.x, p.y, p.z); }, [](double x) { return tsqrt(x); }, o13, code,
+            n, status, flags);
+        __builtin_amdgcn_wave_barrier();
+        store_dist<G>(a.out, pair, gl, o13, code, n, status, flags, r.iters, (uint32_t)r.steps);
+        __builtin_amdgcn_wave_barrier();
+    };
+    for_each_dist_pair<G, G * K, TIER>(grp, a, body);
+}
+#endif  // GK_IN(13)
 
 }  // namespace gk
 
@@ -3012,7 +3069,8 @@ __global__ __launch_bounds__(64, MINW) void dist_kernel(const gjkepa_dist_args a
 // The product build compiles this file once per part (Makefile: -DGK_PART=p), each object instantiating
 // only its own kernels so the parts compile in parallel: 0 = chain reset, query service and the launch
 // dispatchers, 1 = one-wave query path (fp64 compute), 2 = GJK tiers, 3 = contact tiers, 4 + t = EPA
-// tier t, 10 = one-wave query path (fp32 compute), 11 = fp32 redo, 12 = separation distance tiers.
+// tier t, 10 = one-wave query path (fp32 compute), 11 = fp32 redo, 12 = separation distance tiers,
+// 13 = linear cast tiers.
 // Without GK_PART (diagnostic variant builds) one object holds every part.  The non-template kernels
 // (chain reset, query service) are defined in part 0 only.
 // the one-wave query path in fp32 compute (part 10)
@@ -3239,6 +3297,29 @@ template <typename TIn> hipError_t dist_any(int tier, const gjkepa_dist_args& a,
 }  // namespace
 hipError_t gjkepa_launch_dist(int tier, int vert_dtype, const gjkepa_dist_args& a, hipStream_t s) {
     return vert_dtype == GJKEPA_DTYPE_F32 ? dist_any<float>(tier, a, s) : dist_any<double>(tier, a, s);
+}
+#endif
+
+#if GK_IN(13)
+namespace {
+template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
+hipError_t launch_cast(const gjkepa_cast_args& a, hipStream_t s) {
+    auto kfn = gk::cast_kernel<TIn, G, K, MINW, LH, TIER>;
+    constexpr int GPW = 64 / G;
+    const size_t lds = gk::lds_stride<gk::Lds<double, TIn, G, K, 0, 0>, G>() * GPW;
+    const int grid = grid_cap<G>(a.n_pairs, grid_for(kfn, lds, a.num_cus, a.grid));
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(64), lds, s, a);
+    return hipGetLastError();
+}
+template <typename TIn> hipError_t cast_any(int tier, const gjkepa_cast_args& a, hipStream_t s) {
+    static_assert(GJKEPA_GJK_TIERS == 3 && GJKEPA_G2_G * GJKEPA_G2_K >= GJKEPA_MAX_HULL_VERTS, "the last tier holds every hull");
+    return tier == 0 ? launch_cast<TIn, GJKEPA_G0_G, GJKEPA_G0_K, GJKEPA_K0_MINW, (GJKEPA_G0_LH != 0), 0>(a, s)
+         : tier == 1 ? launch_cast<TIn, GJKEPA_G1_G, GJKEPA_G1_K, GJKEPA_K1_MINW, (GJKEPA_G1_LH != 0), 1>(a, s)
+                     : launch_cast<TIn, GJKEPA_G2_G, GJKEPA_G2_K, GJKEPA_K2_MINW, (GJKEPA_G2_LH != 0), 2>(a, s);
+}
+}  // namespace
+hipError_t gjkepa_launch_cast(int tier, int vert_dtype, const gjkepa_cast_args& a, hipStream_t s) {
+    return vert_dtype == GJKEPA_DTYPE_F32 ? cast_any<float>(tier, a, s) : cast_any<double>(tier, a, s);
 }
 #endif
 

@@ -24,6 +24,8 @@ FLIB_PATH = os.path.join(_HERE, "build", "libgclib_gjkepa.so")
 STATUS_OK, STATUS_EPA_MAXITER, STATUS_DEGENERATE, STATUS_BAD_VERSION, STATUS_BAD_INPUT = 0, 1, 2, 3, 4
 STATUS_DIST_MAXITER = 5                      # distance records only (gjkepa_distance_batch)
 DIST_OVERLAP, DIST_HIT, DIST_FAR = 1, 2, 4   # distance record flag bits
+STATUS_CAST_MAXITER = 6                      # cast records only (gjkepa_cast_batch)
+CAST_IMPACT, CAST_START, CAST_SKIPPED = 1, 2, 4   # cast record flag bits (a miss has none)
 DTYPE_F32, DTYPE_F64 = 0, 1
 PREC_F32, PREC_F64 = 0, 1
 MAX_HULL_VERTS = 256
@@ -41,6 +43,7 @@ EXPORTS = (
     "gjkepa_launch_timing", "gjkepa_launch_timing_read",
     "gjkepa_distance_record_bytes", "gjkepa_distance_workspace_bytes", "gjkepa_distance_batch_device",
     "gjkepa_distance_batch",
+    "gjkepa_cast_record_bytes", "gjkepa_cast_workspace_bytes", "gjkepa_cast_batch_device", "gjkepa_cast_batch",
 )
 COMM_ID_BYTES = 128
 # workspace header word counting the park slots a gjkepa_batch_device call took (diagnostics; csrc/
@@ -67,6 +70,14 @@ DIST64 = np.dtype([
     ("reserved", "i1"), ("iters", "<u4"), ("pad", "<u4"),
 ])
 assert DIST64.itemsize == 128
+# gjkepa_cast_f64 (include/gjkepa.h): one per pair from cast_batch / cast_batch_device; the distance
+# record's layout with toi for the distance and steps for the pad
+CAST64 = np.dtype([
+    ("toi", "<f8"), ("point_a", "<f8", (3,)), ("point_b", "<f8", (3,)), ("normal", "<f8", (3,)),
+    ("lambda", "<f8", (3,)), ("code", "<u4", (3,)), ("n_simplex", "i1"), ("status", "i1"), ("flags", "i1"),
+    ("reserved", "i1"), ("iters", "<u4"), ("steps", "<u4"),
+])
+assert CAST64.itemsize == 128
 
 
 def record_dtype(precision: int) -> np.dtype:
@@ -175,6 +186,16 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.gjkepa_distance_batch.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_dbl, c_vp,
                                           c_i32]
     lib.gjkepa_distance_batch.restype = ctypes.c_int
+    lib.gjkepa_cast_record_bytes.argtypes = []
+    lib.gjkepa_cast_record_bytes.restype = ctypes.c_int
+    lib.gjkepa_cast_workspace_bytes.argtypes = [c_i64]
+    lib.gjkepa_cast_workspace_bytes.restype = c_i64
+    lib.gjkepa_cast_batch_device.argtypes = [c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_dbl, c_vp, c_i32, c_vp, c_vp,
+                                             c_i64, c_vp]
+    lib.gjkepa_cast_batch_device.restype = ctypes.c_int
+    lib.gjkepa_cast_batch.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_dbl, c_vp, c_i32, c_vp,
+                                      c_i32]
+    lib.gjkepa_cast_batch.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -422,6 +443,55 @@ def distance_batch_device(vert_dtype: int, verts_ptr: int, hull_off_ptr: int, hu
                                              int(n_pairs), records_ptr or None, int(records_precision),
                                              float(max_distance), out_ptr, ws_ptr, int(ws_bytes), stream or None)
     _check(rc, "gjkepa_distance_batch_device")
+
+
+# ---- linear cast / time of impact of moving pairs (include/gjkepa.h gjkepa_cast_*) ---------------------
+def cast_workspace_bytes(n_pairs: int) -> int:
+    b = int(load().gjkepa_cast_workspace_bytes(int(n_pairs)))
+    if b < 0:
+        raise GjkEpaError("gjkepa_cast_workspace_bytes: bad arguments")
+    return b
+
+
+def cast_batch(pool: HullPool, motion, tolerance: float, records: np.ndarray | None = None,
+               device: int = 0) -> np.ndarray:
+    """Linear cast of every pair of the pool (host buffers, blocking); returns CAST64 records.
+    motion: (n_pairs, 3) float64, hull B's displacement relative to hull A over the step.  tolerance:
+    the absolute distance at which the hulls count as meeting (finite, > 0).  Flags: CAST_IMPACT (toi in
+    (0, 1)), CAST_START (within tolerance or overlapping at t = 0), none for a miss (toi = 1).
+    records: the pool's contact records (gjkepa_batch output): pairs they call a collision are skipped
+    (CAST_SKIPPED)."""
+    lib = load()
+    out = np.zeros(pool.n_pairs, dtype=CAST64)
+    verts = np.ascontiguousarray(pool.verts)
+    off = np.ascontiguousarray(pool.hull_off, np.int64)
+    cnt = np.ascontiguousarray(pool.hull_cnt, np.int32)
+    prs = np.ascontiguousarray(pool.pairs, np.int32).reshape(-1)
+    mot = np.ascontiguousarray(motion, np.float64).reshape(-1)
+    if mot.size != 3 * pool.n_pairs:
+        raise GjkEpaError("motion: 3 float64 per pair")
+    rec_ptr, rec_prec = None, PREC_F64
+    if records is not None:
+        records = np.ascontiguousarray(records)
+        if records.dtype not in (REC64, REC32) or records.shape != (pool.n_pairs,):
+            raise GjkEpaError("records: one REC64 / REC32 contact record per pair")
+        rec_ptr, rec_prec = _ptr(records), (PREC_F64 if records.dtype == REC64 else PREC_F32)
+    rc = lib.gjkepa_cast_batch(pool.dtype_code, _ptr(verts), verts.size, _ptr(off), _ptr(cnt), cnt.size, _ptr(prs),
+                               pool.n_pairs, _ptr(mot), float(tolerance), rec_ptr, rec_prec, _ptr(out), int(device))
+    _check(rc, "gjkepa_cast_batch")
+    return out
+
+
+def cast_batch_device(vert_dtype: int, verts_ptr: int, hull_off_ptr: int, hull_cnt_ptr: int, pairs_ptr: int,
+                      n_pairs: int, motion_ptr: int, tolerance: float, records_ptr: int, records_precision: int,
+                      out_ptr: int, ws_ptr: int, ws_bytes: int, stream: int = 0) -> None:
+    """Device-resident linear cast (raw device pointers), asynchronous on `stream`; records_ptr 0 /
+    None: no contact records.  Chain it after gjkepa_batch_device on the same stream with that call's
+    output as the records."""
+    rc = load().gjkepa_cast_batch_device(int(vert_dtype), verts_ptr, hull_off_ptr, hull_cnt_ptr, pairs_ptr,
+                                         int(n_pairs), motion_ptr, float(tolerance), records_ptr or None,
+                                         int(records_precision), out_ptr, ws_ptr, int(ws_bytes), stream or None)
+    _check(rc, "gjkepa_cast_batch_device")
 
 
 # ---- multi-GPU (SURVEY.md §8 row e; include/gjkepa.h gjkepa_shard_range / _batch_multi / _comm_*) ------

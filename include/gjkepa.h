@@ -383,6 +383,85 @@ int gjkepa_distance_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_
                           const void* records, int32_t records_precision, double max_distance,
                           void* out, int32_t device);
 
+/* ---- linear cast (time of impact) of moving pairs ---------------------------------------------
+ * The third question about a pair: hull B translates relative to hull A by d = motion[3k .. 3k+2]
+ * (B's displacement minus A's over the step; fp64, always 3 doubles per pair), B(t) = B + t d for t in
+ * [0, 1]: do the hulls come within `tolerance` (an absolute distance tau, finite and > 0) of each
+ * other, when first, and where?  A ray cast is the case of a one-vertex hull A.  Linear motion only:
+ * angular motion is out of scope.
+ * Conservative advancement in fp64 over the distance GJK above, on the same group shapes:
+ *   t = 0; at each step the distance GJK runs on A and B + t d (Minkowski points a - b - t d), the
+ *   simplex carried from the step before by its codes.  OVERLAP at t = 0: START.  A separation
+ *   |point_a - point_b| <= tau: START at step 0, IMPACT with toi = t later.  Otherwise, with n the unit
+ *   normal from B to A, s = n.d and lb the GJK's support gap along n: s <= 0 is a MISS (the plane keeps
+ *   separating); else dt = (lb - tau / 2) / s, t + dt >= 1 is a MISS, and t += dt leaves a gap of
+ *   tau / 2 along n, so every visited time is certified free of contact.
+ *   GJKEPA_STATUS_CAST_MAXITER (no flag, toi = the last time certified free) after 32 advancement
+ *   steps, a step without progress, an OVERLAP after the first step (tau at the resolution of fp64 for
+ *   the pair) or an inner distance run at its 64-iteration cap.
+ * A caller can always advance by toi d: toi = 1 for a MISS.  A pair whose closest approach lies between
+ * tau / 2 and tau may be reported either way.  The time of impact holds for any tau; the record's
+ * normal is the direction between two witness points about tau apart, so the plane certificate below
+ * needs tau above about 1e-7 of the coordinates' magnitude (tau^2 > 2^-52 * magnitude * hull extent).
+ * records: as for gjkepa_distance_batch_device; pairs whose collision byte is set are not computed:
+ *   flag SKIPPED, toi 0.  Bad hull counts, non-finite vertices and a non-finite motion component give
+ *   GJKEPA_STATUS_BAD_INPUT for that pair (bad counts first, then SKIPPED, then the values).
+ *
+ * One record per pair, in the distance record's layout.  An IMPACT record certifies itself: point_a =
+ * sum_k lambda[k] a[ia_k] and point_b = sum_k lambda[k] b[ib_k] + toi d lie in A and B(toi) and are at
+ * most tau apart; min_i normal.a_i - max_j normal.b_j - toi normal.d > 0; and normal.d > 0, so the same
+ * plane separates the hulls at every earlier t.  A MISS record's normal is that of a plane which still
+ * separates at t = 1: min_i normal.a_i - max_j normal.b_j - normal.d > 0.
+ *   toi        time of impact; 1 for a MISS; 0 for START / SKIPPED / bad input
+ *   point_a/b  witness points at time toi in world coordinates (IMPACT, separated START; else 0)
+ *   normal     unit, from B to A (IMPACT, separated START, MISS; else 0)
+ *   lambda, code, n_simplex   the witness points' simplex, as in the distance record (else 0 /
+ *              0xFFFFFFFF / 0)
+ *   status     GJKEPA_STATUS_OK, _BAD_INPUT or _CAST_MAXITER
+ *   flags      GJKEPA_CAST_IMPACT, _START or _SKIPPED; a MISS has none
+ *   iters      GJK iterations over all steps;  steps: advancement steps taken */
+#define GJKEPA_STATUS_CAST_MAXITER 6  /* the cast stopped undecided: toi = the last time certified free */
+#define GJKEPA_CAST_IMPACT  1   /* the hulls come within tolerance at toi, 0 < toi < 1 */
+#define GJKEPA_CAST_START   2   /* within tolerance, or overlapping, at t = 0 */
+#define GJKEPA_CAST_SKIPPED 4   /* skipped: the pair's contact record says collision */
+typedef struct gjkepa_cast_f64 {
+    double   toi;
+    double   point_a[3];
+    double   point_b[3];
+    double   normal[3];
+    double   lambda[3];
+    uint32_t code[3];
+    int8_t   n_simplex;
+    int8_t   status;
+    int8_t   flags;
+    int8_t   reserved;
+    uint32_t iters;
+    uint32_t steps;
+} gjkepa_cast_f64;               /* 128 bytes */
+
+/* Size in bytes of one cast record (128). */
+int gjkepa_cast_record_bytes(void);
+/* Bytes of device workspace for n_pairs pairs (work counters, reset by the call itself; 256-byte
+ * aligned); negative for n_pairs < 0. */
+int64_t gjkepa_cast_workspace_bytes(int64_t n_pairs);
+/* Device buffers, asynchronous on `stream` (hipStream_t or NULL): no allocation, no synchronisation,
+ * every launch on that stream only (a captured graph is a linear chain).  Deterministic.  Records
+ * nothing for gjkepa_launch_timing.  n_pairs == 0 returns 0.
+ * GJKEPA_E_ARG for a bad dtype, a null pointer, a bad records_precision with records != NULL, or a
+ * tolerance that is NaN, infinite or <= 0; GJKEPA_E_WORKSPACE for a workspace below
+ * gjkepa_cast_workspace_bytes. */
+int gjkepa_cast_batch_device(int32_t vert_dtype, const void* verts, const int64_t* hull_off,
+                             const int32_t* hull_cnt, const int32_t* pairs, int64_t n_pairs,
+                             const double* motion, double tolerance,
+                             const void* records, int32_t records_precision,
+                             void* out, void* workspace, int64_t workspace_bytes, void* stream);
+/* Host buffers, blocking; the pool arguments and checks of gjkepa_distance_batch.  motion: 3 n_pairs
+ * doubles.  records: NULL or n_pairs contact records (host memory) of precision records_precision. */
+int gjkepa_cast_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
+                      const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                      const int32_t* pairs, int64_t n_pairs, const double* motion, double tolerance,
+                      const void* records, int32_t records_precision, void* out, int32_t device);
+
 /* ---- whole collision step (host buffers, blocking) ---------------------------------------------
  * The reference caller's `DO a; DO b = a+1; CALL GJKEPA(...)` over a pooled hull set in one call:
  * gjkepa_broadphase_device -> gjkepa_batch_device on the candidate list -> gjkepa_compact_hits_device.
