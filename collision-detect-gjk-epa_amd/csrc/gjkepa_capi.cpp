@@ -1,10 +1,12 @@
 // gjkepa_capi.cpp — the C-ABI of include/gjkepa.h over the tiered HIP kernels.
 //
-// Host-buffer entries (gjkepa_query, gjkepa_batch) own per-device staging buffers that grow as
+// Host-buffer entries (gjkepa_query, gjkepa_batch, ...) own per-device staging buffers that grow as
 // needed and are reused; they are serialised per device by a mutex, so concurrent callers (the
-// reference's `!$OMP PARALLEL DO ... CALL GJKEPA` pattern) are safe.  gjkepa_batch_device never
-// allocates or synchronises: it enqueues a 256-byte counter / tally reset and the tier kernels (2 GJK +
-// 5 EPA tiers, and the contact passes, forked onto a second stream for large batches); each kernel
+// reference's `!$OMP PARALLEL DO ... CALL GJKEPA` pattern) are safe.  Each validates its index
+// structure with check_pool and moves its buffers through one Stage.  gjkepa_batch_device never
+// allocates or synchronises: it enqueues a counter / tally reset and the tier kernels (3 GJK + 6 EPA
+// tiers, the contact passes, forked onto internal streams for large batches, and the fp32 redo launch
+// in fp32 compute; up to 64 pairs take one fused launch instead); each kernel
 // takes 64-pair chunks (or runs of 16) from its own counter.  gjkepa_hull_batch(_device) follow the
 // same pattern for the batched convex-hull kernels (two tiers over one cloud list), and
 // gjkepa_distance_batch(_device) for the separation-distance tiers (a counter reset and three launches on
@@ -71,6 +73,7 @@ struct DevBuf {
         if (e == hipSuccess) cap = want;
         return e;
     }
+    template <typename T> T* as() const { return (T*)p; }
 };
 
 struct HostBuf {                 // pinned host staging (one DMA each way for combined queries)
@@ -496,16 +499,78 @@ int init_device(DeviceState* d, int device) {
     return 0;
 }
 
+// One host-buffer call on `device`: the device's state, locked from construction to destruction (two
+// callers never share a staging buffer between an upload and the copy back), its stream, and the moves
+// between host buffers and staging buffers.  up / room / down / sync remember the first HIP error and do
+// nothing after it, so an entry tests failed() once per phase.
+struct Stage {
+    int rc = 0;                            // device lookup / initialisation (the error is set)
+    DeviceState* d;
+    std::unique_lock<std::mutex> lock;
+    hipError_t err = hipSuccess;
+    const char* what = "";
+    explicit Stage(int device) : d(device_state(device, &rc)) {
+        if (!d) return;
+        lock = std::unique_lock<std::mutex>(d->mu);
+        rc = init_device(d, device);
+    }
+    void note(hipError_t e, const char* w) {
+        if (err == hipSuccess && e != hipSuccess) { err = e; what = w; }
+    }
+    int failed() const { return err == hipSuccess ? 0 : hip_fail(err, what); }
+    void room(DevBuf& b, size_t bytes) {
+        if (err == hipSuccess) note(b.ensure(bytes), "hipMalloc");
+    }
+    void up(DevBuf& b, const void* host, size_t bytes) {      // an absent host buffer is skipped
+        if (!host) return;
+        room(b, bytes);
+        if (err == hipSuccess) note(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, d->stream), "hipMemcpyAsync H2D");
+    }
+    // the hull pool every entry reads (for gjkepa_hull_batch the point pool), with the pair list if there is one
+    void up_pool(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars, const int64_t* hull_off,
+                 const int32_t* hull_cnt, int64_t n_hulls, const int32_t* pairs = nullptr, int64_t n_pairs = 0) {
+        up(d->verts, verts, (size_t)n_vert_scalars * (vert_dtype == GJKEPA_DTYPE_F32 ? 4 : 8));
+        up(d->off, hull_off, (size_t)n_hulls * 8);
+        up(d->cnt, hull_cnt, (size_t)n_hulls * 4);
+        up(d->pairs, pairs, (size_t)n_pairs * 8);
+    }
+    void down(void* host, const DevBuf& b, size_t bytes) {
+        if (err == hipSuccess) note(hipMemcpyAsync(host, b.p, bytes, hipMemcpyDeviceToHost, d->stream), "hipMemcpyAsync D2H");
+    }
+    void sync() {
+        if (err == hipSuccess) note(hipStreamSynchronize(d->stream), "hipStreamSynchronize");
+    }
+};
+
 bool valid_enums(int32_t vert_dtype, int32_t precision) {
     return (vert_dtype == GJKEPA_DTYPE_F32 || vert_dtype == GJKEPA_DTYPE_F64) &&
            (precision == GJKEPA_PREC_F32 || precision == GJKEPA_PREC_F64);
+}
+
+// offset of the collision byte in a contact record of `precision`
+int hit_flag_offset(int32_t precision) {
+    return precision == GJKEPA_PREC_F64 ? (int)offsetof(gjkepa_contact_f64, collision) : (int)offsetof(gjkepa_contact_f32, collision);
 }
 
 }  // namespace
 
 namespace gjkepa_internal {
 int set_error(int code, const std::string& msg) { return fail(code, msg); }
+
+int check_pool(const int32_t* pairs, int64_t n_pairs, const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+               int64_t n_vert_scalars, int64_t max_checked_cnt) {
+    for (int64_t k = 0; pairs && k < 2 * n_pairs; ++k)
+        if (pairs[k] < 0 || pairs[k] >= n_hulls) return fail(GJKEPA_E_ARG, "pair references a missing hull");
+    for (int64_t h = 0; h < n_hulls; ++h) {
+        const int64_t c = hull_cnt[h];
+        if (c >= 1 && c <= max_checked_cnt && (hull_off[h] < 0 || hull_off[h] + 3 * c > n_vert_scalars))
+            return fail(GJKEPA_E_ARG, "hull outside the vertex pool");
+    }
+    return 0;
+}
 }  // namespace gjkepa_internal
+using gjkepa_internal::check_pool;
+using gjkepa_internal::kAnyHullCount;
 
 extern "C" {
 
@@ -616,45 +681,24 @@ int gjkepa_batch(int32_t version, double tol_ff, int32_t vert_dtype, int32_t pre
     if (n_pairs == 0) return 0;
     if (!verts || !hull_off || !hull_cnt || !pairs || !out) return fail(GJKEPA_E_ARG, "null pointer");
     if (n_pairs > INT32_MAX) return fail(GJKEPA_E_ARG, "n_pairs above 2^31-1");
-    // host-side validation of the index structure (device code trusts it)
-    for (int64_t k = 0; k < 2 * n_pairs; ++k)
-        if (pairs[k] < 0 || pairs[k] >= n_hulls) return fail(GJKEPA_E_ARG, "pair references a missing hull");
-    for (int64_t h = 0; h < n_hulls; ++h) {
-        int64_t c = hull_cnt[h];
-        if (c >= 1 && (hull_off[h] < 0 || hull_off[h] + 3 * c > n_vert_scalars))
-            return fail(GJKEPA_E_ARG, "hull outside the vertex pool");
-    }
+    int rc = check_pool(pairs, n_pairs, hull_off, hull_cnt, n_hulls, n_vert_scalars, kAnyHullCount);
+    if (rc) return rc;
     // park slots only for the pairs that can reach the parking EPA tiers
     const int64_t wsb = ws_bytes_for(n_pairs, count_large(pairs, n_pairs, hull_cnt));
-    int rc = 0;
-    DeviceState* d = device_state(device, &rc);
-    if (!d) return rc;
-    std::lock_guard<std::mutex> g(d->mu);
-    if ((rc = init_device(d, device))) return rc;
-    hipError_t e;
-    const size_t esz = vert_dtype == GJKEPA_DTYPE_F32 ? 4 : 8;
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
     const size_t rec = (size_t)gjkepa_record_bytes(precision);
-    if ((e = d->verts.ensure((size_t)n_vert_scalars * esz)) != hipSuccess ||
-        (e = d->off.ensure((size_t)n_hulls * 8)) != hipSuccess ||
-        (e = d->cnt.ensure((size_t)n_hulls * 4)) != hipSuccess ||
-        (e = d->pairs.ensure((size_t)n_pairs * 8)) != hipSuccess ||
-        (e = d->out.ensure((size_t)n_pairs * rec)) != hipSuccess ||
-        (e = d->ws.ensure((size_t)wsb)) != hipSuccess)
-        return hip_fail(e, "hipMalloc");
-    hipStream_t s = d->stream;
-    if ((e = hipMemcpyAsync(d->verts.p, verts, (size_t)n_vert_scalars * esz, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->off.p, hull_off, (size_t)n_hulls * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->cnt.p, hull_cnt, (size_t)n_hulls * 4, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->pairs.p, pairs, (size_t)n_pairs * 8, hipMemcpyHostToDevice, s)) != hipSuccess)
-        return hip_fail(e, "hipMemcpyAsync H2D");
-    rc = enqueue(version, tol_ff, vert_dtype, precision, d->verts.p, (const int64_t*)d->off.p,
-                 (const int32_t*)d->cnt.p, (const int32_t*)d->pairs.p, n_pairs, d->out.p, d->ws.p,
-                 (int64_t)d->ws.cap, s, d->num_cus);
+    st.up_pool(vert_dtype, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls, pairs, n_pairs);
+    st.room(d->out, (size_t)n_pairs * rec);
+    st.room(d->ws, (size_t)wsb);
+    if ((rc = st.failed())) return rc;
+    rc = enqueue(version, tol_ff, vert_dtype, precision, d->verts.p, d->off.as<const int64_t>(), d->cnt.as<const int32_t>(),
+                 d->pairs.as<const int32_t>(), n_pairs, d->out.p, d->ws.p, (int64_t)d->ws.cap, d->stream, d->num_cus);
     if (rc) return rc;
-    if ((e = hipMemcpyAsync(out, d->out.p, (size_t)n_pairs * rec, hipMemcpyDeviceToHost, s)) != hipSuccess)
-        return hip_fail(e, "hipMemcpyAsync D2H");
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-    return 0;
+    st.down(out, d->out, (size_t)n_pairs * rec);
+    st.sync();
+    return st.failed();
 }
 
 // ---- separation distance -------------------------------------------------------------------------
@@ -670,45 +714,79 @@ int64_t gjkepa_distance_workspace_bytes(int64_t n_pairs) {
 namespace {
 static_assert(sizeof(gjkepa_distance_f64) == 128, "gjkepa_distance_f64 layout (gjkepa.py DIST64)");
 static_assert(GJKEPA_GJK_TIERS * sizeof(uint32_t) <= GJKEPA_DIST_WS_BYTES, "one counter per distance tier");
-// the checks the device and the host entry share, before any device work
-int distance_args_ok(int32_t vert_dtype, int64_t n_pairs, const void* records, int32_t records_precision,
-                     double max_distance) {
+static_assert(GJKEPA_CAST_WS_BYTES == GJKEPA_DIST_WS_BYTES, "the per-pair queries share the workspace layout");
+
+// ---- what the per-pair queries (distance, cast) share ----------------------------------------------
+// the checks the device and the host entry share, before any device work; the query's own scalar
+// (max_distance, tolerance) is judged by the entry and reported in its place in the order
+int pair_query_args_ok(int32_t vert_dtype, int64_t n_pairs, const void* records, int32_t records_precision, bool scalar_ok,
+                       const char* scalar_msg) {
     if (n_pairs < 0 || (vert_dtype != GJKEPA_DTYPE_F32 && vert_dtype != GJKEPA_DTYPE_F64))
         return fail(GJKEPA_E_ARG, "bad n_pairs/dtype");
     if (records && records_precision != GJKEPA_PREC_F32 && records_precision != GJKEPA_PREC_F64)
         return fail(GJKEPA_E_ARG, "bad records_precision");
-    if (!(max_distance >= 0.0)) return fail(GJKEPA_E_ARG, "max_distance is NaN or negative");
+    if (!scalar_ok) return fail(GJKEPA_E_ARG, scalar_msg);
     if (n_pairs > INT32_MAX) return fail(GJKEPA_E_ARG, "n_pairs above 2^31-1");
     return 0;
 }
-// the chain: counter reset, then one launch per tier, all on the caller's stream
-int distance_enqueue(int32_t vert_dtype, const void* verts, const int64_t* hull_off, const int32_t* hull_cnt,
-                     const int32_t* pairs, int64_t n_pairs, const void* records, int32_t records_precision,
-                     double max_distance, void* out, void* workspace, int64_t ws_bytes, hipStream_t s, int num_cus) {
-    if (n_pairs == 0) return 0;
-    if (ws_bytes < GJKEPA_DIST_WS_BYTES) return fail(GJKEPA_E_WORKSPACE, "workspace too small");
-    uint32_t* ctr = (uint32_t*)workspace;
+// a query's device-resident arguments but its own scalars
+struct PairQuery {
+    int32_t vert_dtype;
+    const void* verts;
+    const int64_t* hull_off;
+    const int32_t* hull_cnt;
+    const int32_t* pairs;
+    int64_t n_pairs;
+    const void* records;            // optional contact records (nullptr: none), of records_precision
+    int32_t records_precision;
+    void* out;
+    void* workspace;
+    int64_t ws_bytes;
+    hipStream_t stream;
+    int num_cus;                    // 0: the current device's, asked after the checks
+};
+// the chain: counter reset, then one launch per tier, all on the caller's stream.  `a` arrives with the
+// query's own fields set; the fields the argument blocks share by name are filled here.
+template <typename Args, typename Launch>
+int pair_query_enqueue(Args a, const PairQuery& q, const char* name, Launch launch) {
+    if (q.n_pairs == 0) return 0;
+    if (q.ws_bytes < GJKEPA_DIST_WS_BYTES) return fail(GJKEPA_E_WORKSPACE, "workspace too small");
+    uint32_t* ctr = (uint32_t*)q.workspace;
     hipError_t e;
-    if ((e = gjkepa_launch_ws_reset(ctr, GJKEPA_DIST_WS_BYTES / 4, s)) != hipSuccess)
-        return hip_fail(e, "distance workspace reset");
-    gjkepa_dist_args a{};
-    a.verts = verts;
-    a.hull_off = hull_off;
-    a.hull_cnt = hull_cnt;
-    a.pairs = pairs;
-    a.n_pairs = n_pairs;
-    a.records = (const unsigned char*)records;
-    a.rec_stride = records_precision == GJKEPA_PREC_F64 ? (int)sizeof(gjkepa_contact_f64) : (int)sizeof(gjkepa_contact_f32);
-    a.rec_hit_off = records_precision == GJKEPA_PREC_F64 ? (int)offsetof(gjkepa_contact_f64, collision)
-                                                         : (int)offsetof(gjkepa_contact_f32, collision);
-    a.max_distance = max_distance;
-    a.out = out;
-    a.num_cus = num_cus;
+    if ((e = gjkepa_launch_ws_reset(ctr, GJKEPA_DIST_WS_BYTES / 4, q.stream)) != hipSuccess)
+        return hip_fail(e, (std::string(name) + " workspace reset").c_str());
+    a.verts = q.verts;
+    a.hull_off = q.hull_off;
+    a.hull_cnt = q.hull_cnt;
+    a.pairs = q.pairs;
+    a.n_pairs = q.n_pairs;
+    a.records = (const unsigned char*)q.records;
+    a.rec_stride = q.records_precision == GJKEPA_PREC_F64 ? (int)sizeof(gjkepa_contact_f64) : (int)sizeof(gjkepa_contact_f32);
+    a.rec_hit_off = hit_flag_offset(q.records_precision);
+    a.out = q.out;
+    a.num_cus = q.num_cus > 0 ? q.num_cus : num_cus_current();
     for (int t = 0; t < GJKEPA_GJK_TIERS; ++t) {
         a.ctr = ctr + t;
-        if ((e = gjkepa_launch_dist(t, vert_dtype, a, s)) != hipSuccess) return hip_fail(e, "distance tier launch");
+        if ((e = launch(t, q.vert_dtype, a, q.stream)) != hipSuccess) return hip_fail(e, (std::string(name) + " tier launch").c_str());
     }
     return 0;
+}
+// the query of a host entry on its staged buffers: pool, pairs, records in d_rec if given, d_out, d_ws
+PairQuery staged_query(const DeviceState* d, int32_t vert_dtype, int64_t n_pairs, const void* records, int32_t records_precision) {
+    return PairQuery{vert_dtype, d->verts.p, d->off.as<const int64_t>(), d->cnt.as<const int32_t>(), d->pairs.as<const int32_t>(),
+                     n_pairs, records ? d->d_rec.p : nullptr, records_precision, d->d_out.p, d->d_ws.p, (int64_t)d->d_ws.cap,
+                     d->stream, d->num_cus};
+}
+
+int distance_args_ok(int32_t vert_dtype, int64_t n_pairs, const void* records, int32_t records_precision,
+                     double max_distance) {
+    return pair_query_args_ok(vert_dtype, n_pairs, records, records_precision, max_distance >= 0.0,
+                              "max_distance is NaN or negative");
+}
+int distance_enqueue(const PairQuery& q, double max_distance) {
+    gjkepa_dist_args a{};
+    a.max_distance = max_distance;
+    return pair_query_enqueue(a, q, "distance", gjkepa_launch_dist);
 }
 }  // namespace
 
@@ -724,9 +802,9 @@ int gjkepa_distance_batch_device(int32_t vert_dtype, const void* verts, const in
     if (n_pairs > 0 && (!verts || !hull_off || !hull_cnt || !pairs || !out || !workspace))
         return fail(GJKEPA_E_ARG, "null pointer");
     if (n_pairs == 0) return 0;
-    if (workspace_bytes < GJKEPA_DIST_WS_BYTES) return fail(GJKEPA_E_WORKSPACE, "workspace too small");
-    return distance_enqueue(vert_dtype, verts, hull_off, hull_cnt, pairs, n_pairs, records, records_precision,
-                            max_distance, out, workspace, workspace_bytes, (hipStream_t)stream, num_cus_current());
+    return distance_enqueue(PairQuery{vert_dtype, verts, hull_off, hull_cnt, pairs, n_pairs, records, records_precision, out,
+                                      workspace, workspace_bytes, (hipStream_t)stream, 0},
+                            max_distance);
 }
 
 int gjkepa_distance_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
@@ -739,44 +817,19 @@ int gjkepa_distance_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_
     if (rc) return rc;
     if (n_pairs == 0) return 0;
     if (!verts || !hull_off || !hull_cnt || !pairs || !out) return fail(GJKEPA_E_ARG, "null pointer");
-    // host-side validation of the index structure (device code trusts it), as gjkepa_batch
-    for (int64_t k = 0; k < 2 * n_pairs; ++k)
-        if (pairs[k] < 0 || pairs[k] >= n_hulls) return fail(GJKEPA_E_ARG, "pair references a missing hull");
-    for (int64_t h = 0; h < n_hulls; ++h) {
-        int64_t c = hull_cnt[h];
-        if (c >= 1 && (hull_off[h] < 0 || hull_off[h] + 3 * c > n_vert_scalars))
-            return fail(GJKEPA_E_ARG, "hull outside the vertex pool");
-    }
-    DeviceState* d = device_state(device, &rc);
-    if (!d) return rc;
-    std::lock_guard<std::mutex> g(d->mu);
-    if ((rc = init_device(d, device))) return rc;
-    hipError_t e;
-    const size_t esz = vert_dtype == GJKEPA_DTYPE_F32 ? 4 : 8;
-    const size_t rec = records ? (size_t)gjkepa_record_bytes(records_precision) : 0;
-    if ((e = d->verts.ensure((size_t)n_vert_scalars * esz)) != hipSuccess ||
-        (e = d->off.ensure((size_t)n_hulls * 8)) != hipSuccess ||
-        (e = d->cnt.ensure((size_t)n_hulls * 4)) != hipSuccess ||
-        (e = d->pairs.ensure((size_t)n_pairs * 8)) != hipSuccess ||
-        (e = d->d_rec.ensure((size_t)n_pairs * rec)) != hipSuccess ||
-        (e = d->d_out.ensure((size_t)n_pairs * sizeof(gjkepa_distance_f64))) != hipSuccess ||
-        (e = d->d_ws.ensure((size_t)GJKEPA_DIST_WS_BYTES)) != hipSuccess)
-        return hip_fail(e, "hipMalloc");
-    hipStream_t s = d->stream;
-    if ((e = hipMemcpyAsync(d->verts.p, verts, (size_t)n_vert_scalars * esz, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->off.p, hull_off, (size_t)n_hulls * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->cnt.p, hull_cnt, (size_t)n_hulls * 4, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->pairs.p, pairs, (size_t)n_pairs * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (records && (e = hipMemcpyAsync(d->d_rec.p, records, (size_t)n_pairs * rec, hipMemcpyHostToDevice, s)) != hipSuccess))
-        return hip_fail(e, "hipMemcpyAsync H2D");
-    rc = distance_enqueue(vert_dtype, d->verts.p, (const int64_t*)d->off.p, (const int32_t*)d->cnt.p,
-                          (const int32_t*)d->pairs.p, n_pairs, records ? d->d_rec.p : nullptr, records_precision,
-                          max_distance, d->d_out.p, d->d_ws.p, (int64_t)d->d_ws.cap, s, d->num_cus);
-    if (rc) return rc;
-    if ((e = hipMemcpyAsync(out, d->d_out.p, (size_t)n_pairs * sizeof(gjkepa_distance_f64), hipMemcpyDeviceToHost, s)) != hipSuccess)
-        return hip_fail(e, "hipMemcpyAsync D2H");
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-    return 0;
+    if ((rc = check_pool(pairs, n_pairs, hull_off, hull_cnt, n_hulls, n_vert_scalars, kAnyHullCount))) return rc;
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
+    st.up_pool(vert_dtype, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls, pairs, n_pairs);
+    st.up(d->d_rec, records, records ? (size_t)n_pairs * (size_t)gjkepa_record_bytes(records_precision) : 0);
+    st.room(d->d_out, (size_t)n_pairs * sizeof(gjkepa_distance_f64));
+    st.room(d->d_ws, (size_t)GJKEPA_DIST_WS_BYTES);
+    if ((rc = st.failed())) return rc;
+    if ((rc = distance_enqueue(staged_query(d, vert_dtype, n_pairs, records, records_precision), max_distance))) return rc;
+    st.down(out, d->d_out, (size_t)n_pairs * sizeof(gjkepa_distance_f64));
+    st.sync();
+    return st.failed();
 }
 
 // ---- linear cast ---------------------------------------------------------------------------------
@@ -794,46 +847,16 @@ static_assert(sizeof(gjkepa_cast_f64) == 128, "gjkepa_cast_f64 layout (gjkepa.py
 static_assert(offsetof(gjkepa_cast_f64, iters) == offsetof(gjkepa_distance_f64, iters) &&
               offsetof(gjkepa_cast_f64, steps) == offsetof(gjkepa_distance_f64, pad), "the cast record is packed as the distance record");
 static_assert(GJKEPA_GJK_TIERS * sizeof(uint32_t) <= GJKEPA_CAST_WS_BYTES, "one counter per cast tier");
-// the checks the device and the host entry share, before any device work
 int cast_args_ok(int32_t vert_dtype, int64_t n_pairs, const void* records, int32_t records_precision, double tolerance) {
-    if (n_pairs < 0 || (vert_dtype != GJKEPA_DTYPE_F32 && vert_dtype != GJKEPA_DTYPE_F64))
-        return fail(GJKEPA_E_ARG, "bad n_pairs/dtype");
-    if (records && records_precision != GJKEPA_PREC_F32 && records_precision != GJKEPA_PREC_F64)
-        return fail(GJKEPA_E_ARG, "bad records_precision");
-    if (!(tolerance > 0.0) || !(tolerance <= 1.7976931348623157e308))
-        return fail(GJKEPA_E_ARG, "tolerance is NaN, infinite, zero or negative");
-    if (n_pairs > INT32_MAX) return fail(GJKEPA_E_ARG, "n_pairs above 2^31-1");
-    return 0;
+    return pair_query_args_ok(vert_dtype, n_pairs, records, records_precision,
+                              tolerance > 0.0 && tolerance <= 1.7976931348623157e308,
+                              "tolerance is NaN, infinite, zero or negative");
 }
-// the chain: counter reset, then one launch per tier, all on the caller's stream
-int cast_enqueue(int32_t vert_dtype, const void* verts, const int64_t* hull_off, const int32_t* hull_cnt,
-                 const int32_t* pairs, int64_t n_pairs, const double* motion, double tolerance, const void* records,
-                 int32_t records_precision, void* out, void* workspace, int64_t ws_bytes, hipStream_t s, int num_cus) {
-    if (n_pairs == 0) return 0;
-    if (ws_bytes < GJKEPA_CAST_WS_BYTES) return fail(GJKEPA_E_WORKSPACE, "workspace too small");
-    uint32_t* ctr = (uint32_t*)workspace;
-    hipError_t e;
-    if ((e = gjkepa_launch_ws_reset(ctr, GJKEPA_CAST_WS_BYTES / 4, s)) != hipSuccess)
-        return hip_fail(e, "cast workspace reset");
+int cast_enqueue(const PairQuery& q, const double* motion, double tolerance) {
     gjkepa_cast_args a{};
-    a.verts = verts;
-    a.hull_off = hull_off;
-    a.hull_cnt = hull_cnt;
-    a.pairs = pairs;
-    a.n_pairs = n_pairs;
-    a.records = (const unsigned char*)records;
-    a.rec_stride = records_precision == GJKEPA_PREC_F64 ? (int)sizeof(gjkepa_contact_f64) : (int)sizeof(gjkepa_contact_f32);
-    a.rec_hit_off = records_precision == GJKEPA_PREC_F64 ? (int)offsetof(gjkepa_contact_f64, collision)
-                                                         : (int)offsetof(gjkepa_contact_f32, collision);
     a.motion = motion;
     a.tolerance = tolerance;
-    a.out = out;
-    a.num_cus = num_cus;
-    for (int t = 0; t < GJKEPA_GJK_TIERS; ++t) {
-        a.ctr = ctr + t;
-        if ((e = gjkepa_launch_cast(t, vert_dtype, a, s)) != hipSuccess) return hip_fail(e, "cast tier launch");
-    }
-    return 0;
+    return pair_query_enqueue(a, q, "cast", gjkepa_launch_cast);
 }
 }  // namespace
 
@@ -849,9 +872,9 @@ int gjkepa_cast_batch_device(int32_t vert_dtype, const void* verts, const int64_
     if (n_pairs > 0 && (!verts || !hull_off || !hull_cnt || !pairs || !motion || !out || !workspace))
         return fail(GJKEPA_E_ARG, "null pointer");
     if (n_pairs == 0) return 0;
-    if (workspace_bytes < GJKEPA_CAST_WS_BYTES) return fail(GJKEPA_E_WORKSPACE, "workspace too small");
-    return cast_enqueue(vert_dtype, verts, hull_off, hull_cnt, pairs, n_pairs, motion, tolerance, records,
-                        records_precision, out, workspace, workspace_bytes, (hipStream_t)stream, num_cus_current());
+    return cast_enqueue(PairQuery{vert_dtype, verts, hull_off, hull_cnt, pairs, n_pairs, records, records_precision, out,
+                                  workspace, workspace_bytes, (hipStream_t)stream, 0},
+                        motion, tolerance);
 }
 
 int gjkepa_cast_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
@@ -864,47 +887,22 @@ int gjkepa_cast_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scal
     if (rc) return rc;
     if (n_pairs == 0) return 0;
     if (!verts || !hull_off || !hull_cnt || !pairs || !motion || !out) return fail(GJKEPA_E_ARG, "null pointer");
-    // host-side validation of the index structure (device code trusts it), as gjkepa_batch
-    for (int64_t k = 0; k < 2 * n_pairs; ++k)
-        if (pairs[k] < 0 || pairs[k] >= n_hulls) return fail(GJKEPA_E_ARG, "pair references a missing hull");
-    for (int64_t h = 0; h < n_hulls; ++h) {
-        int64_t c = hull_cnt[h];
-        if (c >= 1 && (hull_off[h] < 0 || hull_off[h] + 3 * c > n_vert_scalars))
-            return fail(GJKEPA_E_ARG, "hull outside the vertex pool");
-    }
-    DeviceState* d = device_state(device, &rc);
-    if (!d) return rc;
-    std::lock_guard<std::mutex> g(d->mu);
-    if ((rc = init_device(d, device))) return rc;
-    hipError_t e;
-    const size_t esz = vert_dtype == GJKEPA_DTYPE_F32 ? 4 : 8;
-    const size_t rec = records ? (size_t)gjkepa_record_bytes(records_precision) : 0;
-    if ((e = d->verts.ensure((size_t)n_vert_scalars * esz)) != hipSuccess ||
-        (e = d->off.ensure((size_t)n_hulls * 8)) != hipSuccess ||
-        (e = d->cnt.ensure((size_t)n_hulls * 4)) != hipSuccess ||
-        (e = d->pairs.ensure((size_t)n_pairs * 8)) != hipSuccess ||
-        (e = d->d_motion.ensure((size_t)n_pairs * 24)) != hipSuccess ||
-        (e = d->d_rec.ensure((size_t)n_pairs * rec)) != hipSuccess ||
-        (e = d->d_out.ensure((size_t)n_pairs * sizeof(gjkepa_cast_f64))) != hipSuccess ||
-        (e = d->d_ws.ensure((size_t)GJKEPA_CAST_WS_BYTES)) != hipSuccess)
-        return hip_fail(e, "hipMalloc");
-    hipStream_t s = d->stream;
-    if ((e = hipMemcpyAsync(d->verts.p, verts, (size_t)n_vert_scalars * esz, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->off.p, hull_off, (size_t)n_hulls * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->cnt.p, hull_cnt, (size_t)n_hulls * 4, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->pairs.p, pairs, (size_t)n_pairs * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->d_motion.p, motion, (size_t)n_pairs * 24, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (records && (e = hipMemcpyAsync(d->d_rec.p, records, (size_t)n_pairs * rec, hipMemcpyHostToDevice, s)) != hipSuccess))
-        return hip_fail(e, "hipMemcpyAsync H2D");
-    rc = cast_enqueue(vert_dtype, d->verts.p, (const int64_t*)d->off.p, (const int32_t*)d->cnt.p,
-                      (const int32_t*)d->pairs.p, n_pairs, (const double*)d->d_motion.p, tolerance,
-                      records ? d->d_rec.p : nullptr, records_precision, d->d_out.p, d->d_ws.p, (int64_t)d->d_ws.cap, s,
-                      d->num_cus);
-    if (rc) return rc;
-    if ((e = hipMemcpyAsync(out, d->d_out.p, (size_t)n_pairs * sizeof(gjkepa_cast_f64), hipMemcpyDeviceToHost, s)) != hipSuccess)
-        return hip_fail(e, "hipMemcpyAsync D2H");
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-    return 0;
+    if ((rc = check_pool(pairs, n_pairs, hull_off, hull_cnt, n_hulls, n_vert_scalars, kAnyHullCount))) return rc;
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
+    st.up_pool(vert_dtype, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls, pairs, n_pairs);
+    st.up(d->d_motion, motion, (size_t)n_pairs * 24);
+    st.up(d->d_rec, records, records ? (size_t)n_pairs * (size_t)gjkepa_record_bytes(records_precision) : 0);
+    st.room(d->d_out, (size_t)n_pairs * sizeof(gjkepa_cast_f64));
+    st.room(d->d_ws, (size_t)GJKEPA_CAST_WS_BYTES);
+    if ((rc = st.failed())) return rc;
+    if ((rc = cast_enqueue(staged_query(d, vert_dtype, n_pairs, records, records_precision), d->d_motion.as<const double>(),
+                           tolerance)))
+        return rc;
+    st.down(out, d->d_out, (size_t)n_pairs * sizeof(gjkepa_cast_f64));
+    st.sync();
+    return st.failed();
 }
 
 }  // extern "C"
@@ -1483,47 +1481,40 @@ int gjkepa_hull_batch(int32_t vert_dtype, const void* points, int64_t n_point_sc
         if (face_off[c] < 0 || face_off[c] + gjkepa_hull_face_capacity((int32_t)n) > n_face_slots)
             return fail(GJKEPA_E_ARG, "cloud's face block outside the face buffer");
     }
-    int rc = 0;
-    DeviceState* d = device_state(device, &rc);
-    if (!d) return rc;
-    std::lock_guard<std::mutex> g(d->mu);
-    if ((rc = init_device(d, device))) return rc;
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
     const size_t esz = vert_dtype == GJKEPA_DTYPE_F32 ? 4 : 8;
     const size_t pb = (size_t)n_point_scalars * esz, nc = (size_t)n_clouds;
-    hipError_t e;
-    if ((e = d->verts.ensure(pb)) != hipSuccess || (e = d->off.ensure(nc * 8)) != hipSuccess ||
-        (e = d->cnt.ensure(nc * 4)) != hipSuccess || (e = d->h_foff.ensure(nc * 8)) != hipSuccess ||
-        (e = d->h_faces.ensure((size_t)n_face_slots * 12 + 12)) != hipSuccess ||
-        (e = d->h_nf.ensure(nc * 4)) != hipSuccess || (e = d->h_nv.ensure(nc * 4)) != hipSuccess ||
-        (e = d->h_st.ensure(nc)) != hipSuccess ||
-        (hull_verts && (e = d->h_hv.ensure(pb)) != hipSuccess) ||
-        (vert_idx && (e = d->h_vi.ensure((size_t)n_point_scalars * 4)) != hipSuccess))
-        return hip_fail(e, "hipMalloc");
-    hipStream_t s = d->stream;
-    if ((e = hipMemcpyAsync(d->verts.p, points, pb, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->off.p, cloud_off, nc * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->cnt.p, cloud_cnt, nc * 4, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->h_foff.p, face_off, nc * 8, hipMemcpyHostToDevice, s)) != hipSuccess)
-        return hip_fail(e, "hipMemcpyAsync H2D");
-    rc = gjkepa_hull_batch_device(vert_dtype, d->verts.p, (const int64_t*)d->off.p, (const int32_t*)d->cnt.p,
-                                  n_clouds, (const int64_t*)d->h_foff.p, (int32_t*)d->h_faces.p,
-                                  (int32_t*)d->h_nf.p, (int32_t*)d->h_nv.p, (int8_t*)d->h_st.p,
-                                  hull_verts ? d->h_hv.p : nullptr, vert_idx ? (int32_t*)d->h_vi.p : nullptr, s);
+    st.up_pool(vert_dtype, points, n_point_scalars, cloud_off, cloud_cnt, n_clouds);
+    st.up(d->h_foff, face_off, nc * 8);
+    st.room(d->h_faces, (size_t)n_face_slots * 12 + 12);
+    st.room(d->h_nf, nc * 4);
+    st.room(d->h_nv, nc * 4);
+    st.room(d->h_st, nc);
+    if (hull_verts) st.room(d->h_hv, pb);
+    if (vert_idx) st.room(d->h_vi, (size_t)n_point_scalars * 4);
+    int rc = st.failed();
     if (rc) return rc;
-    if ((e = hipMemcpyAsync(n_faces, d->h_nf.p, nc * 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(n_verts, d->h_nv.p, nc * 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(status, d->h_st.p, nc, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (e = hipStreamSynchronize(s)) != hipSuccess)
-        return hip_fail(e, "hipMemcpyAsync D2H");
+    rc = gjkepa_hull_batch_device(vert_dtype, d->verts.p, d->off.as<const int64_t>(), d->cnt.as<const int32_t>(), n_clouds,
+                                  d->h_foff.as<const int64_t>(), d->h_faces.as<int32_t>(), d->h_nf.as<int32_t>(),
+                                  d->h_nv.as<int32_t>(), d->h_st.as<int8_t>(), hull_verts ? d->h_hv.p : nullptr,
+                                  vert_idx ? d->h_vi.as<int32_t>() : nullptr, d->stream);
+    if (rc) return rc;
+    st.down(n_faces, d->h_nf, nc * 4);
+    st.down(n_verts, d->h_nv, nc * 4);
+    st.down(status, d->h_st, nc);
+    st.sync();
+    if ((rc = st.failed())) return rc;
     // copy back only the written parts: each cloud's faces, hull vertices and vertex indices
     std::vector<int32_t> hf((size_t)n_face_slots * 3);
     std::vector<unsigned char> hh(hull_verts ? pb : 0);
     std::vector<int32_t> hi(vert_idx ? (size_t)n_point_scalars : 0);
-    if ((e = hipMemcpyAsync(hf.data(), d->h_faces.p, hf.size() * 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (hull_verts && (e = hipMemcpyAsync(hh.data(), d->h_hv.p, pb, hipMemcpyDeviceToHost, s)) != hipSuccess) ||
-        (vert_idx && (e = hipMemcpyAsync(hi.data(), d->h_vi.p, hi.size() * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) ||
-        (e = hipStreamSynchronize(s)) != hipSuccess)
-        return hip_fail(e, "hipMemcpyAsync D2H");
+    st.down(hf.data(), d->h_faces, hf.size() * 4);
+    if (hull_verts) st.down(hh.data(), d->h_hv, pb);
+    if (vert_idx) st.down(hi.data(), d->h_vi, hi.size() * 4);
+    st.sync();
+    if ((rc = st.failed())) return rc;
     for (int64_t c = 0; c < n_clouds; ++c) {
         const int64_t nf = n_faces[c], nv = n_verts[c];
         if (nf) std::memcpy(faces + 3 * face_off[c], hf.data() + 3 * face_off[c], (size_t)nf * 12);
@@ -1573,41 +1564,31 @@ int gjkepa_broadphase(int32_t vert_dtype, const void* verts, int64_t n_vert_scal
     *n_pairs = 0;
     if (n_hulls == 0) return 0;
     if (!verts || !hull_off || !hull_cnt) return fail(GJKEPA_E_ARG, "null pointer");
-    for (int64_t h = 0; h < n_hulls; ++h) {
-        const int64_t c = hull_cnt[h];
-        if (c >= 1 && c <= GJKEPA_MAX_HULL_VERTS && (hull_off[h] < 0 || hull_off[h] + 3 * c > n_vert_scalars))
-            return fail(GJKEPA_E_ARG, "hull outside the vertex pool");
-    }
-    int rc = 0;
-    DeviceState* d = device_state(device, &rc);
-    if (!d) return rc;
-    std::lock_guard<std::mutex> g(d->mu);
-    if ((rc = init_device(d, device))) return rc;
-    const size_t esz = vert_dtype == GJKEPA_DTYPE_F32 ? 4 : 8;
+    int rc = check_pool(nullptr, 0, hull_off, hull_cnt, n_hulls, n_vert_scalars, GJKEPA_MAX_HULL_VERTS);
+    if (rc) return rc;
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
     const int64_t wsb = gjkepa_broadphase_ws_bytes(n_hulls, max_pairs);
     if (wsb < 0) return fail(GJKEPA_E_HIP, "broad phase workspace query failed");
-    hipError_t e;
-    if ((e = d->verts.ensure((size_t)n_vert_scalars * esz)) != hipSuccess || (e = d->off.ensure((size_t)n_hulls * 8)) != hipSuccess ||
-        (e = d->cnt.ensure((size_t)n_hulls * 4)) != hipSuccess || (e = d->b_pairs.ensure((size_t)max_pairs * 8 + 8)) != hipSuccess ||
-        (e = d->b_count.ensure(8)) != hipSuccess || (e = d->b_ws.ensure((size_t)wsb)) != hipSuccess)
-        return hip_fail(e, "hipMalloc");
-    hipStream_t s = d->stream;
-    if ((e = hipMemcpyAsync(d->verts.p, verts, (size_t)n_vert_scalars * esz, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->off.p, hull_off, (size_t)n_hulls * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->cnt.p, hull_cnt, (size_t)n_hulls * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
-        return hip_fail(e, "hipMemcpyAsync H2D");
-    rc = gjkepa_broadphase_device(vert_dtype, d->verts.p, (const int64_t*)d->off.p, (const int32_t*)d->cnt.p, n_hulls,
-                                  (int32_t*)d->b_pairs.p, max_pairs, (int64_t*)d->b_count.p, d->b_ws.p,
-                                  (int64_t)d->b_ws.cap, s);
+    st.up_pool(vert_dtype, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls);
+    st.room(d->b_pairs, (size_t)max_pairs * 8 + 8);
+    st.room(d->b_count, 8);
+    st.room(d->b_ws, (size_t)wsb);
+    if ((rc = st.failed())) return rc;
+    rc = gjkepa_broadphase_device(vert_dtype, d->verts.p, d->off.as<const int64_t>(), d->cnt.as<const int32_t>(), n_hulls,
+                                  d->b_pairs.as<int32_t>(), max_pairs, d->b_count.as<int64_t>(), d->b_ws.p,
+                                  (int64_t)d->b_ws.cap, d->stream);
     if (rc) return rc;
-    if ((e = hipMemcpyAsync(n_pairs, d->b_count.p, 8, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (e = hipStreamSynchronize(s)) != hipSuccess)
-        return hip_fail(e, "hipMemcpyAsync D2H");
+    st.down(n_pairs, d->b_count, 8);
+    st.sync();
+    if ((rc = st.failed())) return rc;
     const int64_t m = *n_pairs < max_pairs ? *n_pairs : max_pairs;
-    if (m > 0 && ((e = hipMemcpyAsync(pairs, d->b_pairs.p, (size_t)m * 8, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-                  (e = hipStreamSynchronize(s)) != hipSuccess))
-        return hip_fail(e, "hipMemcpyAsync D2H");
-    return 0;
+    if (m > 0) {
+        st.down(pairs, d->b_pairs, (size_t)m * 8);
+        st.sync();
+    }
+    return st.failed();
 }
 
 // ---- contact-list compaction (include/gjkepa.h) ---------------------
@@ -1633,9 +1614,7 @@ int gjkepa_compact_hits_device(int32_t precision, const void* records, int64_t n
     if (need < 0) return fail(GJKEPA_E_HIP, "workspace query failed");
     if (workspace_bytes < need) return fail(GJKEPA_E_WORKSPACE, "workspace too small");
     const int rb = gjkepa_record_bytes(precision);
-    const int flag = precision == GJKEPA_PREC_F64 ? (int)offsetof(gjkepa_contact_f64, collision)
-                                                  : (int)offsetof(gjkepa_contact_f32, collision);
-    e = gjkepa_enqueue_compact(records, n_pairs, rb, flag, hit_idx, hits, n_hits, workspace, s);
+    e = gjkepa_enqueue_compact(records, n_pairs, rb, hit_flag_offset(precision), hit_idx, hits, n_hits, workspace, s);
     return e == hipSuccess ? 0 : hip_fail(e, "compaction launch");
 }
 
@@ -1652,43 +1631,33 @@ int gjkepa_collide(int32_t version, double tol_ff, int32_t vert_dtype, int32_t p
     if (n_candidates) *n_candidates = 0;
     if (n_hulls == 0) return 0;
     if (!verts || !hull_off || !hull_cnt) return fail(GJKEPA_E_ARG, "null pointer");
-    for (int64_t h = 0; h < n_hulls; ++h) {
-        const int64_t c = hull_cnt[h];
-        if (c >= 1 && c <= GJKEPA_MAX_HULL_VERTS && (hull_off[h] < 0 || hull_off[h] + 3 * c > n_vert_scalars))
-            return fail(GJKEPA_E_ARG, "hull outside the vertex pool");
-    }
-    int rc = 0;
-    DeviceState* d = device_state(device, &rc);
-    if (!d) return rc;
-    std::lock_guard<std::mutex> g(d->mu);
-    if ((rc = init_device(d, device))) return rc;
-    const size_t esz = vert_dtype == GJKEPA_DTYPE_F32 ? 4 : 8;
+    int rc = check_pool(nullptr, 0, hull_off, hull_cnt, n_hulls, n_vert_scalars, GJKEPA_MAX_HULL_VERTS);
+    if (rc) return rc;
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
     const size_t rec = (size_t)gjkepa_record_bytes(precision);
     hipStream_t s = d->stream;
-    hipError_t e;
-    if ((e = d->verts.ensure((size_t)n_vert_scalars * esz)) != hipSuccess || (e = d->off.ensure((size_t)n_hulls * 8)) != hipSuccess ||
-        (e = d->cnt.ensure((size_t)n_hulls * 4)) != hipSuccess || (e = d->b_count.ensure(8)) != hipSuccess ||
-        (e = d->c_n.ensure(8)) != hipSuccess)
-        return hip_fail(e, "hipMalloc");
-    if ((e = hipMemcpyAsync(d->verts.p, verts, (size_t)n_vert_scalars * esz, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->off.p, hull_off, (size_t)n_hulls * 8, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d->cnt.p, hull_cnt, (size_t)n_hulls * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
-        return hip_fail(e, "hipMemcpyAsync H2D");
+    st.up_pool(vert_dtype, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls);
+    st.room(d->b_count, 8);
+    st.room(d->c_n, 8);
+    if ((rc = st.failed())) return rc;
     // broad phase: a list of 8 candidates per hull first; one more pass at the exact size if it was cut
     int64_t cap = n_hulls * 8 > 1024 ? n_hulls * 8 : 1024, ncand = 0;
     for (int pass = 0; pass < 2; ++pass) {
         if (cap > INT32_MAX) return fail(GJKEPA_E_ARG, "candidate list above 2^31-1 pairs");
         const int64_t wsb = gjkepa_broadphase_ws_bytes(n_hulls, cap);
         if (wsb < 0) return fail(GJKEPA_E_HIP, "broad phase workspace query failed");
-        if ((e = d->b_pairs.ensure((size_t)cap * 8 + 8)) != hipSuccess || (e = d->b_ws.ensure((size_t)wsb)) != hipSuccess)
-            return hip_fail(e, "hipMalloc");
-        rc = gjkepa_broadphase_device(vert_dtype, d->verts.p, (const int64_t*)d->off.p, (const int32_t*)d->cnt.p,
-                                      n_hulls, (int32_t*)d->b_pairs.p, cap, (int64_t*)d->b_count.p, d->b_ws.p,
+        st.room(d->b_pairs, (size_t)cap * 8 + 8);
+        st.room(d->b_ws, (size_t)wsb);
+        if ((rc = st.failed())) return rc;
+        rc = gjkepa_broadphase_device(vert_dtype, d->verts.p, d->off.as<const int64_t>(), d->cnt.as<const int32_t>(), n_hulls,
+                                      d->b_pairs.as<int32_t>(), cap, d->b_count.as<int64_t>(), d->b_ws.p,
                                       (int64_t)d->b_ws.cap, s);
         if (rc) return rc;
-        if ((e = hipMemcpyAsync(&ncand, d->b_count.p, 8, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-            (e = hipStreamSynchronize(s)) != hipSuccess)
-            return hip_fail(e, "hipMemcpyAsync D2H");
+        st.down(&ncand, d->b_count, 8);
+        st.sync();
+        if ((rc = st.failed())) return rc;
         if (ncand <= cap) break;
         cap = ncand;
     }
@@ -1701,32 +1670,31 @@ int gjkepa_collide(int32_t version, double tol_ff, int32_t vert_dtype, int32_t p
     for (int64_t h = 0; h < n_hulls && !large; ++h) large = hull_cnt[h] > kParkMinHull;
     const int64_t wsn = ws_bytes_for(ncand, large ? ncand : 0), wsc = gjkepa_compact_ws_bytes(ncand);
     if (wsc < 0) return fail(GJKEPA_E_HIP, "compaction workspace query failed");
-    if ((e = d->out.ensure((size_t)ncand * rec)) != hipSuccess || (e = d->ws.ensure((size_t)wsn)) != hipSuccess ||
-        (e = d->c_idx.ensure((size_t)ncand * 4)) != hipSuccess || (e = d->c_hits.ensure((size_t)ncand * rec)) != hipSuccess ||
-        (e = d->c_ws.ensure((size_t)wsc)) != hipSuccess)
-        return hip_fail(e, "hipMalloc");
-    if ((rc = enqueue(version, tol_ff, vert_dtype, precision, d->verts.p, (const int64_t*)d->off.p,
-                      (const int32_t*)d->cnt.p, (const int32_t*)d->b_pairs.p, ncand, d->out.p, d->ws.p,
-                      (int64_t)d->ws.cap, s, d->num_cus)))
+    st.room(d->out, (size_t)ncand * rec);
+    st.room(d->ws, (size_t)wsn);
+    st.room(d->c_idx, (size_t)ncand * 4);
+    st.room(d->c_hits, (size_t)ncand * rec);
+    st.room(d->c_ws, (size_t)wsc);
+    if ((rc = st.failed())) return rc;
+    if ((rc = enqueue(version, tol_ff, vert_dtype, precision, d->verts.p, d->off.as<const int64_t>(), d->cnt.as<const int32_t>(),
+                      d->b_pairs.as<const int32_t>(), ncand, d->out.p, d->ws.p, (int64_t)d->ws.cap, s, d->num_cus)))
         return rc;
-    const int flag = precision == GJKEPA_PREC_F64 ? (int)offsetof(gjkepa_contact_f64, collision)
-                                                  : (int)offsetof(gjkepa_contact_f32, collision);
-    if ((e = gjkepa_enqueue_compact(d->out.p, ncand, (int)rec, flag, (int32_t*)d->c_idx.p, d->c_hits.p,
-                                    (int64_t*)d->c_n.p, d->c_ws.p, s)) != hipSuccess)
-        return hip_fail(e, "compaction launch");
+    const hipError_t e = gjkepa_enqueue_compact(d->out.p, ncand, (int)rec, hit_flag_offset(precision), d->c_idx.as<int32_t>(),
+                                                d->c_hits.p, d->c_n.as<int64_t>(), d->c_ws.p, s);
+    if (e != hipSuccess) return hip_fail(e, "compaction launch");
     int64_t nh = 0;
-    if ((e = hipMemcpyAsync(&nh, d->c_n.p, 8, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-        (e = hipStreamSynchronize(s)) != hipSuccess)
-        return hip_fail(e, "hipMemcpyAsync D2H");
+    st.down(&nh, d->c_n, 8);
+    st.sync();
+    if ((rc = st.failed())) return rc;
     *n_contacts = nh;
     const int64_t m = nh < max_contacts ? nh : max_contacts;
     if (m > 0) {
         std::vector<int32_t> idx((size_t)m), cand((size_t)ncand * 2);
-        if ((e = hipMemcpyAsync(idx.data(), d->c_idx.p, (size_t)m * 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-            (e = hipMemcpyAsync(cand.data(), d->b_pairs.p, (size_t)ncand * 8, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-            (e = hipMemcpyAsync(out, d->c_hits.p, (size_t)m * rec, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-            (e = hipStreamSynchronize(s)) != hipSuccess)
-            return hip_fail(e, "hipMemcpyAsync D2H");
+        st.down(idx.data(), d->c_idx, (size_t)m * 4);
+        st.down(cand.data(), d->b_pairs, (size_t)ncand * 8);
+        st.down(out, d->c_hits, (size_t)m * rec);
+        st.sync();
+        if ((rc = st.failed())) return rc;
         for (int64_t k = 0; k < m; ++k) {
             pairs[2 * k] = cand[2 * (size_t)idx[k]];
             pairs[2 * k + 1] = cand[2 * (size_t)idx[k] + 1];

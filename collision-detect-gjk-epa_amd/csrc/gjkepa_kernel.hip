@@ -3277,49 +3277,51 @@ hipError_t gjkepa_launch_gjk(int tier, int vert_dtype, int precision, const gjke
 
 #endif
 
-#if GK_IN(12)
+#if GK_IN(12) || GK_IN(13)
 namespace {
-template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
-hipError_t launch_dist(const gjkepa_dist_args& a, hipStream_t s) {
-    auto kfn = gk::dist_kernel<TIn, G, K, MINW, LH, TIER>;
+// The distance and the cast tiers launch alike, on GJK tier t's group shape.  FAM names the kernel family:
+// FAM::kernel<TIn, G, K, MINW, LH, TIER> and its waves per SIMD, FAM::minw[tier].
+template <typename FAM, typename TIn, int G, int K, bool LH, int TIER, typename ARGS>
+hipError_t launch_pair_tier(const ARGS& a, hipStream_t s) {
+    auto kfn = FAM::template kernel<TIn, G, K, FAM::minw[TIER], LH, TIER>;
     constexpr int GPW = 64 / G;
     const size_t lds = gk::lds_stride<gk::Lds<double, TIn, G, K, 0, 0>, G>() * GPW;
     const int grid = grid_cap<G>(a.n_pairs, grid_for(kfn, lds, a.num_cus, a.grid));
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(64), lds, s, a);
     return hipGetLastError();
 }
-template <typename TIn> hipError_t dist_any(int tier, const gjkepa_dist_args& a, hipStream_t s) {
+template <typename FAM, typename TIn, typename ARGS> hipError_t pair_tier_any(int tier, const ARGS& a, hipStream_t s) {
     static_assert(GJKEPA_GJK_TIERS == 3 && GJKEPA_G2_G * GJKEPA_G2_K >= GJKEPA_MAX_HULL_VERTS, "the last tier holds every hull");
-    return tier == 0 ? launch_dist<TIn, GJKEPA_G0_G, GJKEPA_G0_K, GJKEPA_D0_MINW, (GJKEPA_G0_LH != 0), 0>(a, s)
-         : tier == 1 ? launch_dist<TIn, GJKEPA_G1_G, GJKEPA_G1_K, GJKEPA_D1_MINW, (GJKEPA_G1_LH != 0), 1>(a, s)
-                     : launch_dist<TIn, GJKEPA_G2_G, GJKEPA_G2_K, GJKEPA_D2_MINW, (GJKEPA_G2_LH != 0), 2>(a, s);
+    return tier == 0 ? launch_pair_tier<FAM, TIn, GJKEPA_G0_G, GJKEPA_G0_K, (GJKEPA_G0_LH != 0), 0>(a, s)
+         : tier == 1 ? launch_pair_tier<FAM, TIn, GJKEPA_G1_G, GJKEPA_G1_K, (GJKEPA_G1_LH != 0), 1>(a, s)
+                     : launch_pair_tier<FAM, TIn, GJKEPA_G2_G, GJKEPA_G2_K, (GJKEPA_G2_LH != 0), 2>(a, s);
 }
 }  // namespace
+#endif
+
+#if GK_IN(12)
+namespace {
+struct DistTiers {
+    static constexpr int minw[3] = {GJKEPA_D0_MINW, GJKEPA_D1_MINW, GJKEPA_D2_MINW};
+    template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
+    static constexpr auto kernel = gk::dist_kernel<TIn, G, K, MINW, LH, TIER>;
+};
+}  // namespace
 hipError_t gjkepa_launch_dist(int tier, int vert_dtype, const gjkepa_dist_args& a, hipStream_t s) {
-    return vert_dtype == GJKEPA_DTYPE_F32 ? dist_any<float>(tier, a, s) : dist_any<double>(tier, a, s);
+    return vert_dtype == GJKEPA_DTYPE_F32 ? pair_tier_any<DistTiers, float>(tier, a, s) : pair_tier_any<DistTiers, double>(tier, a, s);
 }
 #endif
 
 #if GK_IN(13)
 namespace {
-template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
-hipError_t launch_cast(const gjkepa_cast_args& a, hipStream_t s) {
-    auto kfn = gk::cast_kernel<TIn, G, K, MINW, LH, TIER>;
-    constexpr int GPW = 64 / G;
-    const size_t lds = gk::lds_stride<gk::Lds<double, TIn, G, K, 0, 0>, G>() * GPW;
-    const int grid = grid_cap<G>(a.n_pairs, grid_for(kfn, lds, a.num_cus, a.grid));
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(64), lds, s, a);
-    return hipGetLastError();
-}
-template <typename TIn> hipError_t cast_any(int tier, const gjkepa_cast_args& a, hipStream_t s) {
-    static_assert(GJKEPA_GJK_TIERS == 3 && GJKEPA_G2_G * GJKEPA_G2_K >= GJKEPA_MAX_HULL_VERTS, "the last tier holds every hull");
-    return tier == 0 ? launch_cast<TIn, GJKEPA_G0_G, GJKEPA_G0_K, GJKEPA_K0_MINW, (GJKEPA_G0_LH != 0), 0>(a, s)
-         : tier == 1 ? launch_cast<TIn, GJKEPA_G1_G, GJKEPA_G1_K, GJKEPA_K1_MINW, (GJKEPA_G1_LH != 0), 1>(a, s)
-                     : launch_cast<TIn, GJKEPA_G2_G, GJKEPA_G2_K, GJKEPA_K2_MINW, (GJKEPA_G2_LH != 0), 2>(a, s);
-}
+struct CastTiers {
+    static constexpr int minw[3] = {GJKEPA_K0_MINW, GJKEPA_K1_MINW, GJKEPA_K2_MINW};
+    template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
+    static constexpr auto kernel = gk::cast_kernel<TIn, G, K, MINW, LH, TIER>;
+};
 }  // namespace
 hipError_t gjkepa_launch_cast(int tier, int vert_dtype, const gjkepa_cast_args& a, hipStream_t s) {
-    return vert_dtype == GJKEPA_DTYPE_F32 ? cast_any<float>(tier, a, s) : cast_any<double>(tier, a, s);
+    return vert_dtype == GJKEPA_DTYPE_F32 ? pair_tier_any<CastTiers, float>(tier, a, s) : pair_tier_any<CastTiers, double>(tier, a, s);
 }
 #endif
 

@@ -108,10 +108,15 @@ def load(path: str | None = None) -> ctypes.CDLL:
         raise GjkEpaError(f"{p} not built; run `make -C collision-detect-gjk-epa_amd`")
     lib = ctypes.CDLL(p)
     c_i32, c_i64, c_dbl, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
+    # the size queries: *_workspace_bytes(n_pairs) -> int64, *_record_bytes(void) -> int
+    for q in ("gjkepa", "gjkepa_distance", "gjkepa_cast", "gjkepa_compact"):
+        fn = getattr(lib, q + "_workspace_bytes")
+        fn.argtypes, fn.restype = [c_i64], c_i64
+    for q in ("gjkepa_distance", "gjkepa_cast"):
+        fn = getattr(lib, q + "_record_bytes")
+        fn.argtypes, fn.restype = [], ctypes.c_int
     lib.gjkepa_record_bytes.argtypes = [c_i32]
     lib.gjkepa_record_bytes.restype = ctypes.c_int
-    lib.gjkepa_workspace_bytes.argtypes = [c_i64]
-    lib.gjkepa_workspace_bytes.restype = c_i64
     lib.gjkepa_last_error.restype = ctypes.c_char_p
     lib.gjkepa_version_string.restype = ctypes.c_char_p
     lib.gjkepa_query.argtypes = [c_i32, c_dbl, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32]
@@ -140,8 +145,6 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.gjkepa_broadphase_device.restype = ctypes.c_int
     lib.gjkepa_synth_scene.argtypes = [ctypes.c_uint64, c_i64, c_i64, c_i32, c_i32, c_dbl, c_i32, c_vp, c_vp, c_vp]
     lib.gjkepa_synth_scene.restype = c_i64
-    lib.gjkepa_compact_workspace_bytes.argtypes = [c_i64]
-    lib.gjkepa_compact_workspace_bytes.restype = c_i64
     lib.gjkepa_compact_hits_device.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]
     lib.gjkepa_compact_hits_device.restype = ctypes.c_int
     lib.gjkepa_batch_warm_device.argtypes = [c_i32, c_dbl, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64,
@@ -176,20 +179,12 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.gjkepa_launch_timing.restype = ctypes.c_int
     lib.gjkepa_launch_timing_read.argtypes = [c_vp, c_i32]
     lib.gjkepa_launch_timing_read.restype = ctypes.c_int
-    lib.gjkepa_distance_record_bytes.argtypes = []
-    lib.gjkepa_distance_record_bytes.restype = ctypes.c_int
-    lib.gjkepa_distance_workspace_bytes.argtypes = [c_i64]
-    lib.gjkepa_distance_workspace_bytes.restype = c_i64
     lib.gjkepa_distance_batch_device.argtypes = [c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_dbl, c_vp, c_vp,
                                                  c_i64, c_vp]
     lib.gjkepa_distance_batch_device.restype = ctypes.c_int
     lib.gjkepa_distance_batch.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_dbl, c_vp,
                                           c_i32]
     lib.gjkepa_distance_batch.restype = ctypes.c_int
-    lib.gjkepa_cast_record_bytes.argtypes = []
-    lib.gjkepa_cast_record_bytes.restype = ctypes.c_int
-    lib.gjkepa_cast_workspace_bytes.argtypes = [c_i64]
-    lib.gjkepa_cast_workspace_bytes.restype = c_i64
     lib.gjkepa_cast_batch_device.argtypes = [c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_dbl, c_vp, c_i32, c_vp, c_vp,
                                              c_i64, c_vp]
     lib.gjkepa_cast_batch_device.restype = ctypes.c_int
@@ -320,17 +315,33 @@ def synth_pairs(seed: int, n_pairs: int, n_min: int = 32, n_max: int = 32, r_max
     return HullPool(verts, off, cnt, prs.reshape(-1, 2))
 
 
-def gjkepa_batch(pool: HullPool, version: int = 2, tol_ff: float = 1.0, precision: int = PREC_F64,
-                 device: int = 0) -> np.ndarray:
-    """Host-buffer batch on the GPU; returns a structured array of contact records."""
-    lib = load()
-    out = np.zeros(pool.n_pairs, dtype=record_dtype(precision))
+def _pool_args(pool: HullPool):
+    """The pool's contiguous arrays (to be kept alive over the call) and the argument run the pair-list
+    host entries share: verts, n_vert_scalars, hull_off, hull_cnt, n_hulls, pairs, n_pairs."""
     verts = np.ascontiguousarray(pool.verts)
     off = np.ascontiguousarray(pool.hull_off, np.int64)
     cnt = np.ascontiguousarray(pool.hull_cnt, np.int32)
     prs = np.ascontiguousarray(pool.pairs, np.int32).reshape(-1)
-    rc = lib.gjkepa_batch(int(version), float(tol_ff), pool.dtype_code, int(precision), _ptr(verts), verts.size,
-                          _ptr(off), _ptr(cnt), cnt.size, _ptr(prs), pool.n_pairs, _ptr(out), int(device))
+    return (verts, off, cnt, prs), (_ptr(verts), verts.size, _ptr(off), _ptr(cnt), cnt.size, _ptr(prs), pool.n_pairs)
+
+
+def _records_arg(records, n_pairs: int):
+    """Optional contact records of a pair list: (contiguous array or None, its pointer, its precision)."""
+    if records is None:
+        return None, None, PREC_F64
+    records = np.ascontiguousarray(records)
+    if records.dtype not in (REC64, REC32) or records.shape != (n_pairs,):
+        raise GjkEpaError("records: one REC64 / REC32 contact record per pair")
+    return records, _ptr(records), (PREC_F64 if records.dtype == REC64 else PREC_F32)
+
+
+def gjkepa_batch(pool: HullPool, version: int = 2, tol_ff: float = 1.0, precision: int = PREC_F64,
+                 device: int = 0) -> np.ndarray:
+    """Host-buffer batch on the GPU; returns a structured array of contact records."""
+    out = np.zeros(pool.n_pairs, dtype=record_dtype(precision))
+    keep, pool_args = _pool_args(pool)
+    rc = load().gjkepa_batch(int(version), float(tol_ff), pool.dtype_code, int(precision), *pool_args, _ptr(out),
+                             int(device))
     _check(rc, "gjkepa_batch")
     return out
 
@@ -415,20 +426,11 @@ def distance_batch(pool: HullPool, records: np.ndarray | None = None, max_distan
     returns DIST64 records.  records: the pool's contact records (gjkepa_batch output, REC64 or REC32):
     pairs they call a collision are skipped (flag DIST_HIT); None: overlaps are found here (DIST_OVERLAP).
     max_distance: pairs proven farther apart stop early (flag DIST_FAR, distance = the lower bound)."""
-    lib = load()
     out = np.zeros(pool.n_pairs, dtype=DIST64)
-    verts = np.ascontiguousarray(pool.verts)
-    off = np.ascontiguousarray(pool.hull_off, np.int64)
-    cnt = np.ascontiguousarray(pool.hull_cnt, np.int32)
-    prs = np.ascontiguousarray(pool.pairs, np.int32).reshape(-1)
-    rec_ptr, rec_prec = None, PREC_F64
-    if records is not None:
-        records = np.ascontiguousarray(records)
-        if records.dtype not in (REC64, REC32) or records.shape != (pool.n_pairs,):
-            raise GjkEpaError("records: one REC64 / REC32 contact record per pair")
-        rec_ptr, rec_prec = _ptr(records), (PREC_F64 if records.dtype == REC64 else PREC_F32)
-    rc = lib.gjkepa_distance_batch(pool.dtype_code, _ptr(verts), verts.size, _ptr(off), _ptr(cnt), cnt.size, _ptr(prs),
-                                   pool.n_pairs, rec_ptr, rec_prec, float(max_distance), _ptr(out), int(device))
+    keep, pool_args = _pool_args(pool)
+    records, rec_ptr, rec_prec = _records_arg(records, pool.n_pairs)
+    rc = load().gjkepa_distance_batch(pool.dtype_code, *pool_args, rec_ptr, rec_prec, float(max_distance), _ptr(out),
+                                      int(device))
     _check(rc, "gjkepa_distance_batch")
     return out
 
@@ -461,23 +463,14 @@ def cast_batch(pool: HullPool, motion, tolerance: float, records: np.ndarray | N
     (0, 1)), CAST_START (within tolerance or overlapping at t = 0), none for a miss (toi = 1).
     records: the pool's contact records (gjkepa_batch output): pairs they call a collision are skipped
     (CAST_SKIPPED)."""
-    lib = load()
     out = np.zeros(pool.n_pairs, dtype=CAST64)
-    verts = np.ascontiguousarray(pool.verts)
-    off = np.ascontiguousarray(pool.hull_off, np.int64)
-    cnt = np.ascontiguousarray(pool.hull_cnt, np.int32)
-    prs = np.ascontiguousarray(pool.pairs, np.int32).reshape(-1)
+    keep, pool_args = _pool_args(pool)
     mot = np.ascontiguousarray(motion, np.float64).reshape(-1)
     if mot.size != 3 * pool.n_pairs:
         raise GjkEpaError("motion: 3 float64 per pair")
-    rec_ptr, rec_prec = None, PREC_F64
-    if records is not None:
-        records = np.ascontiguousarray(records)
-        if records.dtype not in (REC64, REC32) or records.shape != (pool.n_pairs,):
-            raise GjkEpaError("records: one REC64 / REC32 contact record per pair")
-        rec_ptr, rec_prec = _ptr(records), (PREC_F64 if records.dtype == REC64 else PREC_F32)
-    rc = lib.gjkepa_cast_batch(pool.dtype_code, _ptr(verts), verts.size, _ptr(off), _ptr(cnt), cnt.size, _ptr(prs),
-                               pool.n_pairs, _ptr(mot), float(tolerance), rec_ptr, rec_prec, _ptr(out), int(device))
+    records, rec_ptr, rec_prec = _records_arg(records, pool.n_pairs)
+    rc = load().gjkepa_cast_batch(pool.dtype_code, *pool_args, _ptr(mot), float(tolerance), rec_ptr, rec_prec, _ptr(out),
+                                  int(device))
     _check(rc, "gjkepa_cast_batch")
     return out
 
@@ -507,16 +500,11 @@ def gjkepa_batch_multi(pool: HullPool, devices, version: int = 2, tol_ff: float 
                        precision: int = PREC_F64) -> np.ndarray:
     """One process driving several devices: pool's pairs in contiguous shards, shard s on devices[s];
     returns every record in pair order (bit-identical to gjkepa_batch)."""
-    lib = load()
     out = np.zeros(pool.n_pairs, dtype=record_dtype(precision))
-    verts = np.ascontiguousarray(pool.verts)
-    off = np.ascontiguousarray(pool.hull_off, np.int64)
-    cnt = np.ascontiguousarray(pool.hull_cnt, np.int32)
-    prs = np.ascontiguousarray(pool.pairs, np.int32).reshape(-1)
+    keep, pool_args = _pool_args(pool)
     dev = np.ascontiguousarray(devices, np.int32)
-    rc = lib.gjkepa_batch_multi(int(version), float(tol_ff), pool.dtype_code, int(precision), _ptr(verts), verts.size,
-                                _ptr(off), _ptr(cnt), cnt.size, _ptr(prs), pool.n_pairs, _ptr(out), _ptr(dev),
-                                dev.size)
+    rc = load().gjkepa_batch_multi(int(version), float(tol_ff), pool.dtype_code, int(precision), *pool_args, _ptr(out),
+                                   _ptr(dev), dev.size)
     _check(rc, "gjkepa_batch_multi")
     return out
 
