@@ -10,8 +10,8 @@
 // takes 64-pair chunks (or runs of 16) from its own counter.  gjkepa_hull_batch(_device) follow the
 // same pattern for the batched convex-hull kernels (two tiers over one cloud list), and
 // gjkepa_distance_batch(_device) for the separation-distance tiers (a counter reset and three launches on
-// the caller's stream, counters in a workspace of their own), and gjkepa_cast_batch(_device) for the
-// linear-cast tiers (the same chain shape).
+// the caller's stream, counters in a workspace of their own), and gjkepa_cast_batch(_device) and
+// gjkepa_manifold_batch(_device) for the linear-cast and the contact-manifold tiers (the same chain shape).
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -719,11 +719,12 @@ static_assert(GJKEPA_CAST_WS_BYTES == GJKEPA_DIST_WS_BYTES, "the per-pair querie
 // ---- what the per-pair queries (distance, cast) share ----------------------------------------------
 // the checks the device and the host entry share, before any device work; the query's own scalar
 // (max_distance, tolerance) is judged by the entry and reported in its place in the order
-int pair_query_args_ok(int32_t vert_dtype, int64_t n_pairs, const void* records, int32_t records_precision, bool scalar_ok,
+// records_given: the entry reads contact records (optional and present, or required), so their precision counts
+int pair_query_args_ok(int32_t vert_dtype, int64_t n_pairs, bool records_given, int32_t records_precision, bool scalar_ok,
                        const char* scalar_msg) {
     if (n_pairs < 0 || (vert_dtype != GJKEPA_DTYPE_F32 && vert_dtype != GJKEPA_DTYPE_F64))
         return fail(GJKEPA_E_ARG, "bad n_pairs/dtype");
-    if (records && records_precision != GJKEPA_PREC_F32 && records_precision != GJKEPA_PREC_F64)
+    if (records_given && records_precision != GJKEPA_PREC_F32 && records_precision != GJKEPA_PREC_F64)
         return fail(GJKEPA_E_ARG, "bad records_precision");
     if (!scalar_ok) return fail(GJKEPA_E_ARG, scalar_msg);
     if (n_pairs > INT32_MAX) return fail(GJKEPA_E_ARG, "n_pairs above 2^31-1");
@@ -780,7 +781,7 @@ PairQuery staged_query(const DeviceState* d, int32_t vert_dtype, int64_t n_pairs
 
 int distance_args_ok(int32_t vert_dtype, int64_t n_pairs, const void* records, int32_t records_precision,
                      double max_distance) {
-    return pair_query_args_ok(vert_dtype, n_pairs, records, records_precision, max_distance >= 0.0,
+    return pair_query_args_ok(vert_dtype, n_pairs, records != nullptr, records_precision, max_distance >= 0.0,
                               "max_distance is NaN or negative");
 }
 int distance_enqueue(const PairQuery& q, double max_distance) {
@@ -848,7 +849,7 @@ static_assert(offsetof(gjkepa_cast_f64, iters) == offsetof(gjkepa_distance_f64, 
               offsetof(gjkepa_cast_f64, steps) == offsetof(gjkepa_distance_f64, pad), "the cast record is packed as the distance record");
 static_assert(GJKEPA_GJK_TIERS * sizeof(uint32_t) <= GJKEPA_CAST_WS_BYTES, "one counter per cast tier");
 int cast_args_ok(int32_t vert_dtype, int64_t n_pairs, const void* records, int32_t records_precision, double tolerance) {
-    return pair_query_args_ok(vert_dtype, n_pairs, records, records_precision,
+    return pair_query_args_ok(vert_dtype, n_pairs, records != nullptr, records_precision,
                               tolerance > 0.0 && tolerance <= 1.7976931348623157e308,
                               "tolerance is NaN, infinite, zero or negative");
 }
@@ -901,6 +902,80 @@ int gjkepa_cast_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scal
                            tolerance)))
         return rc;
     st.down(out, d->d_out, (size_t)n_pairs * sizeof(gjkepa_cast_f64));
+    st.sync();
+    return st.failed();
+}
+
+// ---- contact manifold ----------------------------------------------------------------------------
+int gjkepa_manifold_record_bytes(void) { return (int)sizeof(gjkepa_manifold_f64); }
+
+int64_t gjkepa_manifold_workspace_bytes(int64_t n_pairs) {
+    if (n_pairs < 0) return GJKEPA_E_ARG;
+    return GJKEPA_MANIFOLD_WS_BYTES;   // the tier launches' chunk counters: independent of the batch size
+}
+
+}  // extern "C"
+
+namespace {
+static_assert(sizeof(gjkepa_manifold_f64) == 160 && offsetof(gjkepa_manifold_f64, code) == 128 &&
+              offsetof(gjkepa_manifold_f64, n_points) == 148 && offsetof(gjkepa_manifold_f64, area) == 152,
+              "gjkepa_manifold_f64 layout (gjkepa.py MANIFOLD64; the kernel stores it as 20 8-byte words)");
+static_assert(GJKEPA_MANIFOLD_WS_BYTES == GJKEPA_DIST_WS_BYTES, "the per-pair queries share the workspace layout");
+static_assert(offsetof(gjkepa_contact_f64, status) == offsetof(gjkepa_contact_f64, collision) + 2 &&
+              offsetof(gjkepa_contact_f32, status) == offsetof(gjkepa_contact_f32, collision) + 2 &&
+              offsetof(gjkepa_contact_f64, collision_normal) == 8 && offsetof(gjkepa_contact_f32, collision_normal) == 4 &&
+              offsetof(gjkepa_contact_f64, collision_point) == 32 && offsetof(gjkepa_contact_f32, collision_point) == 16,
+              "the contact-record fields the manifold kernel reads");
+// the manifold's records are required: their precision is judged whether or not the pointer is there
+// (the pointer itself with the other null checks, after an empty batch has returned)
+int manifold_args_ok(int32_t vert_dtype, int64_t n_pairs, int32_t records_precision, double margin) {
+    return pair_query_args_ok(vert_dtype, n_pairs, true, records_precision,
+                              margin >= 0.0 && margin <= 1.7976931348623157e308, "margin is NaN, infinite or negative");
+}
+int manifold_enqueue(const PairQuery& q, double margin) {
+    gjkepa_manifold_args a{};
+    a.margin = margin;
+    return pair_query_enqueue(a, q, "manifold", gjkepa_launch_manifold);
+}
+}  // namespace
+
+extern "C" {
+
+int gjkepa_manifold_batch_device(int32_t vert_dtype, const void* verts, const int64_t* hull_off,
+                                 const int32_t* hull_cnt, const int32_t* pairs, int64_t n_pairs,
+                                 const void* records, int32_t records_precision, double margin,
+                                 void* out, void* workspace, int64_t workspace_bytes, void* stream) {
+    const gjkepa_internal::Range range_("gjkepa_manifold_batch_device (chain enqueue)");
+    int rc = manifold_args_ok(vert_dtype, n_pairs, records_precision, margin);
+    if (rc) return rc;
+    if (n_pairs == 0) return 0;
+    if (!verts || !hull_off || !hull_cnt || !pairs || !records || !out || !workspace) return fail(GJKEPA_E_ARG, "null pointer");
+    return manifold_enqueue(PairQuery{vert_dtype, verts, hull_off, hull_cnt, pairs, n_pairs, records, records_precision, out,
+                                      workspace, workspace_bytes, (hipStream_t)stream, 0},
+                            margin);
+}
+
+int gjkepa_manifold_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
+                          const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                          const int32_t* pairs, int64_t n_pairs, const void* records,
+                          int32_t records_precision, double margin, void* out, int32_t device) {
+    const gjkepa_internal::Range range_("gjkepa_manifold_batch (H2D, chain, D2H)");
+    if (n_hulls < 0 || n_vert_scalars < 0) return fail(GJKEPA_E_ARG, "bad sizes");
+    int rc = manifold_args_ok(vert_dtype, n_pairs, records_precision, margin);
+    if (rc) return rc;
+    if (n_pairs == 0) return 0;
+    if (!verts || !hull_off || !hull_cnt || !pairs || !records || !out) return fail(GJKEPA_E_ARG, "null pointer");
+    if ((rc = check_pool(pairs, n_pairs, hull_off, hull_cnt, n_hulls, n_vert_scalars, kAnyHullCount))) return rc;
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
+    st.up_pool(vert_dtype, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls, pairs, n_pairs);
+    st.up(d->d_rec, records, (size_t)n_pairs * (size_t)gjkepa_record_bytes(records_precision));
+    st.room(d->d_out, (size_t)n_pairs * sizeof(gjkepa_manifold_f64));
+    st.room(d->d_ws, (size_t)GJKEPA_MANIFOLD_WS_BYTES);
+    if ((rc = st.failed())) return rc;
+    if ((rc = manifold_enqueue(staged_query(d, vert_dtype, n_pairs, records, records_precision), margin))) return rc;
+    st.down(out, d->d_out, (size_t)n_pairs * sizeof(gjkepa_manifold_f64));
     st.sync();
     return st.failed();
 }

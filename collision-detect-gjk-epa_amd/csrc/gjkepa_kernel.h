@@ -424,6 +424,43 @@ struct gjkepa_cast_args {
 };
 hipError_t gjkepa_launch_cast(int tier, int vert_dtype, const gjkepa_cast_args& a, hipStream_t s);
 
+// ---- contact manifold (gjkepa_manifold_batch_device): one pass over the two hulls of every pair the
+// contact records call a collision, on the distance tiers' shapes, pair schedule (for_each_dist_pair with
+// its filter taking the hits instead of skipping them) and workspace layout.
+// Waves per SIMD of the manifold tiers.  The kernel needs 173 to 181 VGPRs; at three waves (168) it spills
+// 2 to 8 of them.  A/B per tier, two rounds in one session (profiles/r14/ab_minw.txt, "minw t0 t1 t2"; C2 runs
+// tier 0 only, the other two launches scan and find nothing): tier 0 at three waves C2 1.456 -> 1.41 ms, C4
+// unchanged; tier 2 at three C4 14.6 -> 12.0 ms; tier 1 at three C4 -0.2 ms.  A tier at three waves has
+// half as many workgroups again, which costs a launch that finds no pair of its bracket 0.08 ms (C2): taken
+// for tier 2, not for tier 1.
+#ifndef GJKEPA_M0_MINW
+#define GJKEPA_M0_MINW 3
+#endif
+#ifndef GJKEPA_M1_MINW
+#define GJKEPA_M1_MINW 2
+#endif
+#ifndef GJKEPA_M2_MINW
+#define GJKEPA_M2_MINW 3
+#endif
+#define GJKEPA_MANIFOLD_WS_BYTES GJKEPA_DIST_WS_BYTES
+struct gjkepa_manifold_args {
+    const void* verts;
+    const int64_t* hull_off;
+    const int32_t* hull_cnt;
+    const int32_t* pairs;
+    int64_t n_pairs;
+    const unsigned char* records;   // the contact records of the same pair list (required)
+    int rec_stride;                 // bytes per contact record (128: fp64 fields, 64: fp32), and the offset of
+    int rec_hit_off;                // its collision byte (the status byte is two further on)
+    double margin;                  // thickness of the two features (finite, >= 0)
+    uint32_t* ctr;                  // this launch's chunk counter (zero at launch)
+    void* out;                      // gjkepa_manifold_f64 records
+    int grid;                       // <= 0: occupancy x CUs
+    int num_cus;
+    static constexpr int kSkipFlag = GJKEPA_MANIFOLD_NO_HIT;
+};
+hipError_t gjkepa_launch_manifold(int tier, int vert_dtype, const gjkepa_manifold_args& a, hipStream_t s);
+
 hipError_t gjkepa_launch_gjk(int tier, int vert_dtype, int precision, const gjkepa_gjk_args& a, hipStream_t s);
 hipError_t gjkepa_launch_epa(int tier, int vert_dtype, int precision, const gjkepa_epa_args& a, hipStream_t s);
 // contact tiers take the same argument block (route_code = GJKEPA_ROUTE_CT0 + tier; next_code unused)

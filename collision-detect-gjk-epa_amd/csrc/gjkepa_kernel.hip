@@ -38,11 +38,14 @@
 #else
 #define GK_IN(p) 1
 #endif
-#if GK_IN(12)
-#include "dist_simplex.h"       // the distance GJK's simplex arithmetic (host and device)
+#if GK_IN(12) || GK_IN(14)
+#include "dist_simplex.h"       // the distance GJK's simplex arithmetic (host and device); part 14: the record helpers' constants
 #endif
 #if GK_IN(13)
 #include "cast_advance.h"       // the linear cast: conservative advancement over the distance GJK
+#endif
+#if GK_IN(14)
+#include "manifold_clip.h"      // the contact manifold's plane geometry (host and device)
 #endif
 
 namespace gk {
@@ -2872,7 +2875,7 @@ __global__ __launch_bounds__(64) void ws_reset_kernel(uint32_t* ws, int n32, uin
 }
 #endif  // GK_IN(0)
 
-#if GK_IN(12) || GK_IN(13)
+#if GK_IN(12) || GK_IN(13) || GK_IN(14)
 // ---------------------------------------------------------------- separation distance
 // gjkepa_distance_f64: 13 doubles (distance, point_a, point_b, normal, lambda), code[3], the four
 // int8 fields, iters, pad (the cast record: steps).  Its 16 8-byte words are stored from registers, word j by group lane j % G.
@@ -2904,6 +2907,31 @@ DEV void store_dist_empty(void* out, int64_t pair, int status, int flags) {
     w[15] = 0ull;
 }
 
+// gjkepa_manifold_f64 with nothing computed (bad input, or no usable hit): 20 8-byte words by one lane
+DEV void store_manifold_empty(void* out, int64_t pair, int status, int flags) {
+    uint64_t* w = reinterpret_cast<uint64_t*>(out) + pair * 20;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) w[j] = 0ull;
+    w[16] = ~0ull;
+    w[17] = ~0ull;
+    w[18] = (uint64_t)(((uint32_t)(status & 0xff) << 8) | ((uint32_t)(flags & 0xff) << 16)) << 32;
+    w[19] = 0ull;
+}
+// Does pair p's contact record (stride 128: fp64 fields, else fp32) describe a collision the manifold is
+// built for: the collision byte set, status OK, a finite normal that is not zero?  n: the normal, widened.
+DEV bool manifold_hit(const unsigned char* records, int64_t p, int stride, int hit_off, V3<double>& n) {
+    const unsigned char* r = records + p * (int64_t)stride;
+    if (stride == (int)sizeof(gjkepa_contact_f64)) {
+        const double* d = reinterpret_cast<const double*>(r);
+        n = vmk<double>(d[1], d[2], d[3]);
+    } else {
+        const float* d = reinterpret_cast<const float*>(r);
+        n = vmk<double>((double)d[1], (double)d[2], (double)d[3]);
+    }
+    const bool usable = isfinite(n.x) && isfinite(n.y) && isfinite(n.z) && (n.x != 0.0 || n.y != 0.0 || n.z != 0.0);
+    return r[hit_off] != 0 && r[hit_off + 2] == GJKEPA_STATUS_OK && usable;
+}
+
 // The distance tiers' work distribution: for_each_routed_pair's dense schedule (64-pair chunks and a
 // tail of small units from the launch's counter, Units / tail_unit / groups_take), with the pairs of
 // a unit chosen lane-parallel from the hull counts and the contact records instead of a route byte:
@@ -2912,8 +2940,9 @@ DEV void store_dist_empty(void* out, int64_t pair, int status, int flags) {
 // candidate pairs are hits (C2: 73%): handed to the groups they would leave three groups in four of
 // every round idle (measured, 2^20 C2 pairs: 1.99 ms with every pair handed out, 1.40 ms with this
 // filter; 2^22 C4 pairs 16.1 -> 10.5 ms).  ARGS: gjkepa_dist_args, or the cast's gjkepa_cast_args (the
-// same fields and its own skip flag).
-template <int G, int CAP, int TIER, typename ARGS, typename F>
+// same fields and its own skip flag).  HITS (the contact manifold, gjkepa_manifold_args): the filter
+// is turned round, the groups get the usable hits and the lane answers every other pair with NO_HIT.
+template <int G, int CAP, int TIER, bool HITS = false, typename ARGS, typename F>
 DEV void for_each_dist_pair(const Grp<G>& grp, const ARGS& a, F&& f) {
     constexpr int LO = TIER == 0 ? 0 : TIER == 1 ? GJKEPA_G0_G * GJKEPA_G0_K : GJKEPA_G1_G * GJKEPA_G1_K;
     static_assert(LO < CAP, "tier brackets ascend");
@@ -2931,7 +2960,15 @@ DEV void for_each_dist_pair(const Grp<G>& grp, const ARGS& a, F&& f) {
             const int64_t p = p0 + grp.lane;
             const int na = a.hull_cnt[a.pairs[2 * p]], nb = a.hull_cnt[a.pairs[2 * p + 1]];
             const int nmax = na > nb ? na : nb;
-            if (na < 1 || nb < 1 || na > GJKEPA_MAX_HULL_VERTS || nb > GJKEPA_MAX_HULL_VERTS) {
+            if constexpr (HITS) {
+                V3<double> n;
+                if (na < 1 || nb < 1 || na > GJKEPA_MAX_HULL_VERTS || nb > GJKEPA_MAX_HULL_VERTS) {
+                    if (TIER == 0) store_manifold_empty(a.out, p, GJKEPA_STATUS_BAD_INPUT, 0);
+                } else if (nmax > LO && nmax <= CAP) {
+                    if (manifold_hit(a.records, p, a.rec_stride, a.rec_hit_off, n)) take = true;
+                    else store_manifold_empty(a.out, p, GJKEPA_STATUS_OK, ARGS::kSkipFlag);
+                }
+            } else if (na < 1 || nb < 1 || na > GJKEPA_MAX_HULL_VERTS || nb > GJKEPA_MAX_HULL_VERTS) {
                 if (TIER == 0) store_dist_empty(a.out, p, GJKEPA_STATUS_BAD_INPUT, 0);
             } else if (nmax > LO && nmax <= CAP) {
                 if (a.records && a.records[p * (int64_t)a.rec_stride + a.rec_hit_off] != 0)
@@ -3010,7 +3047,7 @@ __global__ __launch_bounds__(64, MINW) void dist_kernel(const gjkepa_dist_args a
     for_each_dist_pair<G, G * K, TIER>(grp, a, body);
 }
 #endif  // GK_IN(12)
-#endif  // GK_IN(12) || GK_IN(13)
+#endif  // GK_IN(12) || GK_IN(13) || GK_IN(14)
 
 #if GK_IN(13)
 // ---------------------------------------------------------------- linear cast
@@ -3063,6 +3100,150 @@ __global__ __launch_bounds__(64, MINW) void cast_kernel(const gjkepa_cast_args a
 }
 #endif  // GK_IN(13)
 
+#if GK_IN(14)
+// ---------------------------------------------------------------- contact manifold
+// Manifold kernel of tier TIER: the distance tiers' shapes and schedule, one group per usable hit.  The
+// heights, the feature membership and the members' ranks (steps 1 and 2 of the definition,
+// include/gjkepa.h) are lane-parallel over the hull image: one dot per vertex, the group's max / min,
+// then a ballot per register slot (index k G + lane: lower k first, then lower lane, which is ascending
+// vertex index).  A feature is a list of vertex indices in the group's LDS image beside the hulls (one
+// byte each, as the contact tiers keep their point sets), the coordinates re-read from the hull image;
+// steps 3 to 8 (manifold_clip.h) are group-uniform over those lists.
+static_assert(gkm::kFlagNoHit == GJKEPA_MANIFOLD_NO_HIT && gkm::kFlagDecimated == GJKEPA_MANIFOLD_DECIMATED &&
+              gkm::kFlagFallback == GJKEPA_MANIFOLD_FALLBACK && gkm::kMaxFeature == GJKEPA_MANIFOLD_MAX_FEATURE,
+              "manifold_clip.h against gjkepa.h");
+static_assert(GJKEPA_MAX_HULL_VERTS <= 256, "feature and footprint lists hold vertex indices as bytes");
+template <typename TH, int G, int K> struct MfLds {
+    Lds<double, TH, G, K, 0, 0> hull;
+    uint8_t feat[2][gkm::kMaxFeature], foot[2][gkm::kMaxFeature];
+};
+// manifold_clip.h's accessor over a group's image: every lane of the group reads and writes the same
+// values at the same addresses
+template <typename C, typename L_t> struct MfMem {
+    const C& c;
+    L_t& L;
+    DEV gkm::D3 vert(int h, int i) const {
+        const auto v = c.raw(h, i);
+        return gkm::mk((double)v.x, (double)v.y, (double)v.z);
+    }
+    DEV int feat(int h, int k) const { return L.feat[h][k]; }
+    DEV int foot(int h, int k) const { return L.foot[h][k]; }
+    DEV void set_foot(int h, int k, int i) { L.foot[h][k] = (uint8_t)i; }
+    DEV double sqrt(double x) const { return tsqrt(x); }
+};
+// The record's 20 8-byte words, word j stored by group lane j % G.
+template <int G> DEV void store_manifold(void* out, int64_t pair, int gl, const uint64_t* w20) {
+#pragma unroll
+    for (int j0 = 0; j0 < 20; j0 += G) {
+        const int j = j0 + gl;
+        if (j >= 20) break;
+        uint64_t v = 0ull;
+#pragma unroll
+        for (int i = 0; i < 20; ++i) v = (j == i) ? w20[i] : v;
+        reinterpret_cast<uint64_t*>(out)[pair * 20 + j] = v;
+    }
+}
+// One hull's feature: the members among this lane's K dots t[k] (`low`: the vertices with t <= bound,
+// hull B's side; else t >= bound), counted, ranked in index order and the kept ranks written to list[];
+// returns the count before decimation.
+template <int G, int K> DEV int manifold_feature(const Grp<G>& grp, const double* t, int n, double bound, bool low, uint8_t* list) {
+    uint32_t in = 0;
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const bool m = k * G + grp.gl < n && (low ? t[k] <= bound : t[k] >= bound);
+        in |= (m ? 1u : 0u) << k;
+        cnt += popc(grp.ballot(m));
+    }
+    cnt = grp.uni(cnt);
+    const int step = gkm::decimation_step(cnt);
+    int base = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const bool m = (in >> k) & 1u;
+        const uint64_t mask = grp.ballot(m);
+        const int r = base + mbcnt(mask);
+        if (m && (step == 1 || r % step == 0)) list[step == 1 ? r : r / step] = (uint8_t)(k * G + grp.gl);
+        base += popc(mask);
+    }
+    return cnt;
+}
+
+template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
+__global__ __launch_bounds__(64, MINW) void manifold_kernel(const gjkepa_manifold_args a) {
+    using T = double;
+    using L_t = MfLds<TIn, G, K>;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const Grp<G> grp;
+    L_t& L = *reinterpret_cast<L_t*>(smem + lds_stride<L_t, G>() * (grp.lane / G));
+    const int gl = grp.gl;
+    const TIn* verts = (const TIn*)a.verts;
+    auto body = [&](int64_t pair, const PairMeta& pm) {      // a usable hit of this tier with valid counts
+        using C = Ctx<T, TIn, G, K, 0, 0, LH>;
+        C c{L.hull, grp};
+        c.na = grp.uni(pm.na);
+        c.nb = grp.uni(pm.nb);
+        if (load_hulls(c, verts + pm.oa, verts + pm.ob)) {
+            if (gl == 0) store_manifold_empty(a.out, pair, GJKEPA_STATUS_BAD_INPUT, 0);
+            __builtin_amdgcn_wave_barrier();
+            return;
+        }
+        V3<T> n;
+        manifold_hit(a.records, pair, a.rec_stride, a.rec_hit_off, n);
+        const unsigned char* rec = a.records + pair * (int64_t)a.rec_stride;
+        gkm::D3 cp;
+        if (a.rec_stride == (int)sizeof(gjkepa_contact_f64)) {
+            const double* d = reinterpret_cast<const double*>(rec);
+            cp = gkm::mk(d[4], d[5], d[6]);
+        } else {
+            const float* d = reinterpret_cast<const float*>(rec);
+            cp = gkm::mk((double)d[4], (double)d[5], (double)d[6]);
+        }
+        // step 1: heights (the slots past a hull's count hold its vertex 0 again: no mask)
+        T ta[K], tb[K];
+        T va = -Tol<T>::BIG, vb = Tol<T>::BIG;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const V3<T> p = c.AV(k), q = c.BV(k);
+            ta[k] = n.x * p.x + n.y * p.y + n.z * p.z;
+            tb[k] = n.x * q.x + n.y * q.y + n.z * q.z;
+            va = red_max(ta[k], va);
+            vb = red_min(tb[k], vb);
+        }
+        const T hA = gmax<G>(va) + T(0), hB = gmin<G>(vb) + T(0);     // -0 -> +0
+        // step 2: features
+        const int fa = manifold_feature<G, K>(grp, ta, c.na, hA - a.margin, false, L.feat[0]);
+        const int fb = manifold_feature<G, K>(grp, tb, c.nb, hB + a.margin, true, L.feat[1]);
+        __builtin_amdgcn_wave_barrier();
+        // steps 3 to 8
+        MfMem<C, L_t> mem{c, L};
+        const gkm::Patch p = gkm::clip_manifold(mem, gkm::mk(n.x, n.y, n.z), hA, gkm::decimated_count(fa),
+                                                gkm::decimated_count(fb), cp);
+        const int flags = p.flags | ((fa > gkm::kMaxFeature || fb > gkm::kMaxFeature) ? GJKEPA_MANIFOLD_DECIMATED : 0);
+        uint64_t w[20];
+        w[0] = __builtin_bit_cast(uint64_t, hA - hB);
+        w[1] = __builtin_bit_cast(uint64_t, n.x);
+        w[2] = __builtin_bit_cast(uint64_t, n.y);
+        w[3] = __builtin_bit_cast(uint64_t, n.z);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            w[4 + 3 * k] = __builtin_bit_cast(uint64_t, p.pt[k].x);
+            w[5 + 3 * k] = __builtin_bit_cast(uint64_t, p.pt[k].y);
+            w[6 + 3 * k] = __builtin_bit_cast(uint64_t, p.pt[k].z);
+        }
+        w[16] = (uint64_t)p.code[0] | ((uint64_t)p.code[1] << 32);
+        w[17] = (uint64_t)p.code[2] | ((uint64_t)p.code[3] << 32);
+        w[18] = (uint64_t)(uint32_t)(fa & 0xffff) | ((uint64_t)(uint32_t)(fb & 0xffff) << 16) |
+                ((uint64_t)((uint32_t)(p.n & 0xff) | ((uint32_t)GJKEPA_STATUS_OK << 8) | ((uint32_t)(flags & 0xff) << 16)) << 32);
+        w[19] = __builtin_bit_cast(uint64_t, p.area);
+        __builtin_amdgcn_wave_barrier();
+        store_manifold<G>(a.out, pair, gl, w);
+        __builtin_amdgcn_wave_barrier();
+    };
+    for_each_dist_pair<G, G * K, TIER, true>(grp, a, body);
+}
+#endif  // GK_IN(14)
+
 }  // namespace gk
 
 // ---------------------------------------------------------------- host-side launch table
@@ -3070,7 +3251,7 @@ __global__ __launch_bounds__(64, MINW) void cast_kernel(const gjkepa_cast_args a
 // only its own kernels so the parts compile in parallel: 0 = chain reset, query service and the launch
 // dispatchers, 1 = one-wave query path (fp64 compute), 2 = GJK tiers, 3 = contact tiers, 4 + t = EPA
 // tier t, 10 = one-wave query path (fp32 compute), 11 = fp32 redo, 12 = separation distance tiers,
-// 13 = linear cast tiers.
+// 13 = linear cast tiers, 14 = contact manifold tiers.
 // Without GK_PART (diagnostic variant builds) one object holds every part.  The non-template kernels
 // (chain reset, query service) are defined in part 0 only.
 // the one-wave query path in fp32 compute (part 10)
@@ -3277,15 +3458,16 @@ hipError_t gjkepa_launch_gjk(int tier, int vert_dtype, int precision, const gjke
 
 #endif
 
-#if GK_IN(12) || GK_IN(13)
+#if GK_IN(12) || GK_IN(13) || GK_IN(14)
 namespace {
-// The distance and the cast tiers launch alike, on GJK tier t's group shape.  FAM names the kernel family:
-// FAM::kernel<TIn, G, K, MINW, LH, TIER> and its waves per SIMD, FAM::minw[tier].
+// The distance, cast and manifold tiers launch alike, on GJK tier t's group shape.  FAM names the kernel
+// family: FAM::kernel<TIn, G, K, MINW, LH, TIER>, its waves per SIMD FAM::minw[tier] and a group's LDS
+// image FAM::Image<TIn, G, K>.
 template <typename FAM, typename TIn, int G, int K, bool LH, int TIER, typename ARGS>
 hipError_t launch_pair_tier(const ARGS& a, hipStream_t s) {
     auto kfn = FAM::template kernel<TIn, G, K, FAM::minw[TIER], LH, TIER>;
     constexpr int GPW = 64 / G;
-    const size_t lds = gk::lds_stride<gk::Lds<double, TIn, G, K, 0, 0>, G>() * GPW;
+    const size_t lds = gk::lds_stride<typename FAM::template Image<TIn, G, K>, G>() * GPW;
     const int grid = grid_cap<G>(a.n_pairs, grid_for(kfn, lds, a.num_cus, a.grid));
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(64), lds, s, a);
     return hipGetLastError();
@@ -3305,6 +3487,7 @@ struct DistTiers {
     static constexpr int minw[3] = {GJKEPA_D0_MINW, GJKEPA_D1_MINW, GJKEPA_D2_MINW};
     template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
     static constexpr auto kernel = gk::dist_kernel<TIn, G, K, MINW, LH, TIER>;
+    template <typename TIn, int G, int K> using Image = gk::Lds<double, TIn, G, K, 0, 0>;
 };
 }  // namespace
 hipError_t gjkepa_launch_dist(int tier, int vert_dtype, const gjkepa_dist_args& a, hipStream_t s) {
@@ -3318,10 +3501,26 @@ struct CastTiers {
     static constexpr int minw[3] = {GJKEPA_K0_MINW, GJKEPA_K1_MINW, GJKEPA_K2_MINW};
     template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
     static constexpr auto kernel = gk::cast_kernel<TIn, G, K, MINW, LH, TIER>;
+    template <typename TIn, int G, int K> using Image = gk::Lds<double, TIn, G, K, 0, 0>;
 };
 }  // namespace
 hipError_t gjkepa_launch_cast(int tier, int vert_dtype, const gjkepa_cast_args& a, hipStream_t s) {
     return vert_dtype == GJKEPA_DTYPE_F32 ? pair_tier_any<CastTiers, float>(tier, a, s) : pair_tier_any<CastTiers, double>(tier, a, s);
+}
+#endif
+
+#if GK_IN(14)
+namespace {
+struct ManifoldTiers {
+    static constexpr int minw[3] = {GJKEPA_M0_MINW, GJKEPA_M1_MINW, GJKEPA_M2_MINW};
+    template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
+    static constexpr auto kernel = gk::manifold_kernel<TIn, G, K, MINW, LH, TIER>;
+    template <typename TIn, int G, int K> using Image = gk::MfLds<TIn, G, K>;
+};
+}  // namespace
+hipError_t gjkepa_launch_manifold(int tier, int vert_dtype, const gjkepa_manifold_args& a, hipStream_t s) {
+    return vert_dtype == GJKEPA_DTYPE_F32 ? pair_tier_any<ManifoldTiers, float>(tier, a, s)
+                                          : pair_tier_any<ManifoldTiers, double>(tier, a, s);
 }
 #endif
 

@@ -26,6 +26,8 @@ STATUS_DIST_MAXITER = 5                      # distance records only (gjkepa_dis
 DIST_OVERLAP, DIST_HIT, DIST_FAR = 1, 2, 4   # distance record flag bits
 STATUS_CAST_MAXITER = 6                      # cast records only (gjkepa_cast_batch)
 CAST_IMPACT, CAST_START, CAST_SKIPPED = 1, 2, 4   # cast record flag bits (a miss has none)
+MANIFOLD_NO_HIT, MANIFOLD_DECIMATED, MANIFOLD_FALLBACK = 1, 2, 4   # manifold record flag bits
+MANIFOLD_MAX_FEATURE = 32                    # feature vertices used per hull (gjkepa_manifold_batch)
 DTYPE_F32, DTYPE_F64 = 0, 1
 PREC_F32, PREC_F64 = 0, 1
 MAX_HULL_VERTS = 256
@@ -44,6 +46,8 @@ EXPORTS = (
     "gjkepa_distance_record_bytes", "gjkepa_distance_workspace_bytes", "gjkepa_distance_batch_device",
     "gjkepa_distance_batch",
     "gjkepa_cast_record_bytes", "gjkepa_cast_workspace_bytes", "gjkepa_cast_batch_device", "gjkepa_cast_batch",
+    "gjkepa_manifold_record_bytes", "gjkepa_manifold_workspace_bytes", "gjkepa_manifold_batch_device",
+    "gjkepa_manifold_batch",
 )
 COMM_ID_BYTES = 128
 # workspace header word counting the park slots a gjkepa_batch_device call took (diagnostics; csrc/
@@ -78,6 +82,13 @@ CAST64 = np.dtype([
     ("reserved", "i1"), ("iters", "<u4"), ("steps", "<u4"),
 ])
 assert CAST64.itemsize == 128
+# gjkepa_manifold_f64 (include/gjkepa.h): one per pair from manifold_batch / manifold_batch_device
+MANIFOLD64 = np.dtype([
+    ("depth", "<f8"), ("normal", "<f8", (3,)), ("point", "<f8", (4, 3)), ("code", "<u4", (4,)),
+    ("n_feat_a", "<u2"), ("n_feat_b", "<u2"), ("n_points", "i1"), ("status", "i1"), ("flags", "i1"),
+    ("reserved", "i1"), ("area", "<f8"),
+])
+assert MANIFOLD64.itemsize == 160
 
 
 def record_dtype(precision: int) -> np.dtype:
@@ -109,10 +120,10 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib = ctypes.CDLL(p)
     c_i32, c_i64, c_dbl, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
     # the size queries: *_workspace_bytes(n_pairs) -> int64, *_record_bytes(void) -> int
-    for q in ("gjkepa", "gjkepa_distance", "gjkepa_cast", "gjkepa_compact"):
+    for q in ("gjkepa", "gjkepa_distance", "gjkepa_cast", "gjkepa_manifold", "gjkepa_compact"):
         fn = getattr(lib, q + "_workspace_bytes")
         fn.argtypes, fn.restype = [c_i64], c_i64
-    for q in ("gjkepa_distance", "gjkepa_cast"):
+    for q in ("gjkepa_distance", "gjkepa_cast", "gjkepa_manifold"):
         fn = getattr(lib, q + "_record_bytes")
         fn.argtypes, fn.restype = [], ctypes.c_int
     lib.gjkepa_record_bytes.argtypes = [c_i32]
@@ -191,6 +202,10 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.gjkepa_cast_batch.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_dbl, c_vp, c_i32, c_vp,
                                       c_i32]
     lib.gjkepa_cast_batch.restype = ctypes.c_int
+    lib.gjkepa_manifold_batch_device.argtypes = lib.gjkepa_distance_batch_device.argtypes    # margin for max_distance
+    lib.gjkepa_manifold_batch_device.restype = ctypes.c_int
+    lib.gjkepa_manifold_batch.argtypes = lib.gjkepa_distance_batch.argtypes
+    lib.gjkepa_manifold_batch.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -485,6 +500,41 @@ def cast_batch_device(vert_dtype: int, verts_ptr: int, hull_off_ptr: int, hull_c
                                          int(n_pairs), motion_ptr, float(tolerance), records_ptr or None,
                                          int(records_precision), out_ptr, ws_ptr, int(ws_bytes), stream or None)
     _check(rc, "gjkepa_cast_batch_device")
+
+
+# ---- contact manifold of colliding pairs (include/gjkepa.h gjkepa_manifold_*) --------------------------
+def manifold_workspace_bytes(n_pairs: int) -> int:
+    b = int(load().gjkepa_manifold_workspace_bytes(int(n_pairs)))
+    if b < 0:
+        raise GjkEpaError("gjkepa_manifold_workspace_bytes: bad arguments")
+    return b
+
+
+def manifold_batch(pool: HullPool, records: np.ndarray, margin: float, device: int = 0) -> np.ndarray:
+    """Contact manifold (up to 4 points on hull A's support plane, with feature codes) of every pair of
+    the pool its contact records call a collision (host buffers, blocking); returns MANIFOLD64 records.
+    records: the pool's contact records (gjkepa_batch output, REC64 or REC32), required.  margin: the
+    thickness of the two features, an absolute length (finite, >= 0).  Every other pair: MANIFOLD_NO_HIT."""
+    if records is None:
+        raise GjkEpaError("records: one REC64 / REC32 contact record per pair")
+    out = np.zeros(pool.n_pairs, dtype=MANIFOLD64)
+    keep, pool_args = _pool_args(pool)
+    records, rec_ptr, rec_prec = _records_arg(records, pool.n_pairs)
+    rc = load().gjkepa_manifold_batch(pool.dtype_code, *pool_args, rec_ptr, rec_prec, float(margin), _ptr(out),
+                                      int(device))
+    _check(rc, "gjkepa_manifold_batch")
+    return out
+
+
+def manifold_batch_device(vert_dtype: int, verts_ptr: int, hull_off_ptr: int, hull_cnt_ptr: int, pairs_ptr: int,
+                          n_pairs: int, records_ptr: int, records_precision: int, margin: float, out_ptr: int,
+                          ws_ptr: int, ws_bytes: int, stream: int = 0) -> None:
+    """Device-resident contact manifold (raw device pointers), asynchronous on `stream`.  Chain it after
+    gjkepa_batch_device on the same stream with that call's output as the records."""
+    rc = load().gjkepa_manifold_batch_device(int(vert_dtype), verts_ptr, hull_off_ptr, hull_cnt_ptr, pairs_ptr,
+                                             int(n_pairs), records_ptr or None, int(records_precision),
+                                             float(margin), out_ptr, ws_ptr, int(ws_bytes), stream or None)
+    _check(rc, "gjkepa_manifold_batch_device")
 
 
 # ---- multi-GPU (SURVEY.md §8 row e; include/gjkepa.h gjkepa_shard_range / _batch_multi / _comm_*) ------

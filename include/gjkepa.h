@@ -462,6 +462,99 @@ int gjkepa_cast_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scal
                       const int32_t* pairs, int64_t n_pairs, const double* motion, double tolerance,
                       const void* records, int32_t records_precision, void* out, int32_t device);
 
+/* ---- contact manifold (up to 4 points) of colliding pairs --------------------------------------
+ * The fourth question about a pair, for the pairs a batch calls a collision: a contact patch instead of
+ * the reference's one collision_point, as a solver needs for two boxes resting face to face.  It is
+ * built from the pair's contact record and the two hulls, in fp64 (vertices stored as fp32 or fp64),
+ * with n = the record's collision_normal as doubles, unmodified (an F32 record's is widened):
+ *   1. heights   hA = max_i n.a_i, hB = min_j n.b_j (a height of -0 counts as +0), depth = hA - hB.
+ *   2. features  FA = { i : n.a_i >= hA - margin }, FB = { j : n.b_j <= hB + margin }, each in ascending
+ *      vertex index; margin is an absolute length, finite and >= 0.  At most
+ *      GJKEPA_MANIFOLD_MAX_FEATURE = 32 vertices per hull are used: of a feature of m > 32 vertices the
+ *      vertices of rank r (in index order) with r % ceil(m / 32) == 0, with flag DECIMATED.  A subset of
+ *      a hull's vertices lies inside the hull, so the manifold stays conservative, and a ring (a prism's
+ *      face) thins out evenly.
+ *   3. frame     e = the coordinate axis of the smallest |n| component (the first of equals),
+ *      u = (e x n) / |e x n|, w = n x u; 2-D coordinates (x, y) = ((p - o).u, (p - o).w) about
+ *      o = a[FA[0]]; s = the largest |x| or |y| over the vertices used of both features, the scale of
+ *      every tolerance below.
+ *   4. footprints  the strict 2-D convex hull of each feature, counter-clockwise seen from +n, from the
+ *      lexicographically smallest (x, y, index); collinear points are dropped, the farthest kept.  A
+ *      footprint is a point, a segment or a polygon.
+ *   5. candidates  A's footprint vertices no more than 1e-9 s outside every edge line of B's footprint
+ *      (a segment footprint: within 1e-9 s across it and along its length; a point footprint: within
+ *      1e-9 s of it), then B's against A's footprint, then every proper crossing (both parameters strictly
+ *      inside (0, 1)) of an edge of A with an edge of B in edge order; edges r, q with
+ *      |r x q| <= 1e-9 |r| |q| count as parallel and do not cross.  A segment footprint has one edge.
+ *   6. reduction to at most four points, each an argmax over the candidates in that order, the first of
+ *      equals: p0 = the lexicographically smallest (x, y); p1 = the farthest from p0, kept if farther
+ *      than 1e-9 s; pL / pR = the candidates of the largest triangle (p0, p1, c) to the left / right of
+ *      p0 -> p1, each kept if the triangle's area exceeds 1e-9 s^2.  Reported counter-clockwise:
+ *      p0, pR, p1, pL.  Without any candidate the record holds one point, the contact record's
+ *      collision_point projected onto A's support plane, with flag FALLBACK and no code.
+ *   7. lifting   every point is moved along n onto A's support plane n.x = hA; its partner on B is
+ *      point - depth n.  depth is uniform over the patch: within 2 margin of the depth measured at any
+ *      one of the points (the features are margin thick each).
+ *   8. code per point  ia | ib << 16 as for the warm start and the distance record: a footprint vertex
+ *      of A ia | 0xFFFF << 16, of B 0xFFFF | ib << 16, a crossing the start vertices (in counter-clockwise
+ *      order) of its two edges.  Stable from frame to frame while the features are.  Unused: 0xFFFFFFFF.
+ * The constants 1e-9 and 32 and the pick rule are part of the definition (csrc/manifold_clip.h is its
+ * text, for host and device).
+ * Computed for the pairs whose contact record has the collision byte set, status GJKEPA_STATUS_OK and a
+ * finite, non-zero normal; every other pair gets flag NO_HIT, no points and zeroed fields (codes
+ * 0xFFFFFFFF).  A hull count outside 1 .. GJKEPA_MAX_HULL_VERTS gives GJKEPA_STATUS_BAD_INPUT (zeroed
+ * fields, no flag) whatever the record says; a non-finite vertex gives it for a pair that would be
+ * computed.
+ *   depth      hA - hB along normal
+ *   normal     n, as read from the contact record
+ *   point      n_points points on A's support plane, counter-clockwise seen from +normal; the rest 0
+ *   code       per point, as in step 8
+ *   n_feat_a/b vertices of the two features before decimation
+ *   area       shoelace area of the reported polygon in the plane; 0 below three points */
+#define GJKEPA_MANIFOLD_MAX_FEATURE 32
+#define GJKEPA_MANIFOLD_NO_HIT    1   /* not computed: the contact record is no usable collision */
+#define GJKEPA_MANIFOLD_DECIMATED 2   /* a feature had more than GJKEPA_MANIFOLD_MAX_FEATURE vertices */
+#define GJKEPA_MANIFOLD_FALLBACK  4   /* no candidate: the one point is the projected collision_point */
+typedef struct gjkepa_manifold_f64 {
+    double   depth;
+    double   normal[3];
+    double   point[4][3];
+    uint32_t code[4];
+    uint16_t n_feat_a;
+    uint16_t n_feat_b;
+    int8_t   n_points;
+    int8_t   status;
+    int8_t   flags;
+    int8_t   reserved;
+    double   area;
+} gjkepa_manifold_f64;           /* 160 bytes */
+
+/* Size in bytes of one manifold record (160). */
+int gjkepa_manifold_record_bytes(void);
+/* Bytes of device workspace for n_pairs pairs (work counters, reset by the call itself; 256-byte
+ * aligned); negative for n_pairs < 0. */
+int64_t gjkepa_manifold_workspace_bytes(int64_t n_pairs);
+/* Device buffers, asynchronous on `stream` (hipStream_t or NULL): no allocation, no synchronisation,
+ * every launch on that stream only (a captured graph is a linear chain; chain it after
+ * gjkepa_batch_device with that call's output as `records`).  Deterministic.  Records nothing for
+ * gjkepa_launch_timing.  n_pairs == 0 returns 0.
+ * records: required, the n_pairs contact records (gjkepa_contact_f64 / _f32 by records_precision) of
+ *   the same pair list.
+ * GJKEPA_E_ARG for a bad dtype or records_precision, a margin that is NaN, infinite or negative, or a
+ * null pointer (records among them); GJKEPA_E_WORKSPACE for a workspace below
+ * gjkepa_manifold_workspace_bytes. */
+int gjkepa_manifold_batch_device(int32_t vert_dtype, const void* verts, const int64_t* hull_off,
+                                 const int32_t* hull_cnt, const int32_t* pairs, int64_t n_pairs,
+                                 const void* records, int32_t records_precision, double margin,
+                                 void* out, void* workspace, int64_t workspace_bytes, void* stream);
+/* Host buffers, blocking; the pool arguments and checks of gjkepa_distance_batch.  records: n_pairs
+ * contact records in host memory. */
+int gjkepa_manifold_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
+                          const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                          const int32_t* pairs, int64_t n_pairs,
+                          const void* records, int32_t records_precision, double margin,
+                          void* out, int32_t device);
+
 /* ---- whole collision step (host buffers, blocking) ---------------------------------------------
  * The reference caller's `DO a; DO b = a+1; CALL GJKEPA(...)` over a pooled hull set in one call:
  * gjkepa_broadphase_device -> gjkepa_batch_device on the candidate list -> gjkepa_compact_hits_device.

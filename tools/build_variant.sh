@@ -18,7 +18,7 @@ rm -f $OUT/k[0-9]*.o
 if [ "${SINGLE:-0}" = 1 ]; then
   /opt/rocm/bin/hipcc $F -c $S/gjkepa_kernel.hip -o $OUT/k0.o & PIDS="$!"
 else
-  for p in 0 1 2 3 4 5 6 7 8 9 10 11 12; do
+  for p in 0 1 2 3 4 5 6 7 8 9 10 11 12 13 14; do
     /opt/rocm/bin/hipcc $F -DGK_PART=$p -c $S/gjkepa_kernel.hip -o $OUT/k$p.o & PIDS="$PIDS $!"
   done
 fi

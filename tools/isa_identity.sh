@@ -12,7 +12,7 @@ REV=$(git rev-parse --short "$1")
 F="--offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17 -Wall -Wno-unused-function --cuda-device-only -S"
 emit() {   # emit <tree> <outdir>: masked device assembly of every kernel file of <tree>
   mkdir -p "$2"
-  for p in 0 1 2 3 4 5 6 7 8 9 10 11 12 13; do
+  for p in 0 1 2 3 4 5 6 7 8 9 10 11 12 13 14; do
     /opt/rocm/bin/hipcc $F -DGK_PART=$p "$1/$P/csrc/gjkepa_kernel.hip" -o "$2/gk_part$p.s" 2> /dev/null &
   done
   for k in hull broadphase contacts; do
