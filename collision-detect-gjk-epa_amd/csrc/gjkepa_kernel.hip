@@ -1028,6 +1028,7 @@ CTX_T DEV int epa_seed(CTX& c, EPAST_T& S, V3<T> s0, V3<T> s1, V3<T> s2, V3<T> s
 
 // Closes iteration S.iters (MINLOC of the polytope, termination :956-1015); if EPA goes on, the
 // next iteration's direction (:888-910) replaces S.dir.  ST_CONT, 0 (depth and normal set) or a status.
+// In the refill kernels it runs in the same pass as the epa_grow it closes, after it.
 CTX_T DEV int epa_close(CTX& c, EPAST_T& S, T& depth, V3<T>& normal) {
     const int F2 = S.nf;                                      // :956-969
     const T prev = S.minv;
@@ -1081,7 +1082,8 @@ CTX_T DEV int epa_close(CTX& c, EPAST_T& S, T& depth, V3<T>& normal) {
 // The rest of an iteration along dir = S.dir: support point(s) (:914, :935-944) and the hull of the polytope
 // vertices and the new point(s) (:918-950).  `first`: iteration 1 after epa_seed, which adds the
 // points to the simplex's tetrahedron exactly as hull_build does (no distance save, no unchanged
-// short cut: iteration 1's termination test compares the seed soup's distances).
+// short cut: iteration 1's termination test compares the seed soup's distances).  In the refill kernels
+// it opens a pass: every active group of the wave takes this support step together.
 CTX_T DEV int epa_grow(CTX& c, EPAST_T& S, bool first) {
     constexpr int R = (FC + G - 1) / G;
     auto& E = c.L.u.e;
@@ -2337,7 +2339,12 @@ struct PairQueue {
 
 // EPA tier kernel with group refill: a group whose pair finished takes the next pair between
 // two EPA iterations (once at least REFILL groups of the wave are idle), so a wave no longer
-// runs every round to its slowest pair.  Results are the same as epa_kernel's.
+// runs every round to its slowest pair.  One trip of the loop is one pass of the whole wave:
+// refill (a fresh pair runs epa_seed, or epa_begin when its simplex is not the first tetrahedron),
+// then every active group's epa_grow, then that iteration's epa_close, then park / finish.  The
+// pass ends after the close, so a pair occupies its group for as many passes as it has iterations:
+// it leaves in the pass that ran its last one.  Per pair the calls are epa()'s, in epa()'s order.
+// Results are the same as epa_kernel's.
 template <typename TIn, typename T, int G, int K, int VC, int FC, int MINW, bool LH, int REFILL, int PR>
 __global__ __launch_bounds__(64, MINW) void epa_kernel_refill(const gjkepa_epa_args a) {
     static_assert(!(PR & 2), "refill tiers do not resume parked polytopes");
@@ -2364,6 +2371,7 @@ __global__ __launch_bounds__(64, MINW) void epa_kernel_refill(const gjkepa_epa_a
     EpaState<T, R> S;
     bool active = false;
     bool seeded = false;                 // iteration 1 set up by epa_seed: its support step is pending
+    bool begun = false;                  // iteration 1 run whole by epa_begin: nothing to grow in this pass
     int64_t pair = 0;
     uint32_t gjk_it = 0;
     // final record / park / route for a pair whose EPA ended with status r
@@ -2417,14 +2425,17 @@ __global__ __launch_bounds__(64, MINW) void epa_kernel_refill(const gjkepa_epa_a
             S.iters = 1; S.nf = 0;
             int r = ST_DEFER;
             seeded = false;
+            begun = false;
             if (c.na <= G * K && c.nb <= G * K) {
                 const V3<T> s0 = decode_pt(c, kc[0]), s1 = decode_pt(c, kc[1]), s2 = decode_pt(c, kc[2]), s3 = decode_pt(c, kc[3]);
                 if (gl == 0) tally_route(seed.on ? GJKEPA_TALLY_SEED_HANDED : GJKEPA_TALLY_SEED_OWN);
                 // a fresh pair's iteration 1 joins the common support step
                 r = epa_seed(c, S, s0, s1, s2, s3, seed);
                 seeded = r == 0;
-                if (r == ST_FALLBACK)
+                if (r == ST_FALLBACK) {
                     r = epa_begin(c, S, s0, s1, s2, s3, seed);
+                    begun = r == 0;
+                }
             }
             __builtin_amdgcn_wave_barrier();
             active = r == 0;
@@ -2432,21 +2443,23 @@ __global__ __launch_bounds__(64, MINW) void epa_kernel_refill(const gjkepa_epa_a
         }
         GK_STAMP(SE_LOAD);
         if (active) {
-            // groups that closed an iteration (everything but the ones epa_seed just set up) take the
-            // MINLOC / termination step; every continuing group then takes the support step together
+            // every group takes its iteration's support step together (all but the ones epa_begin just ran
+            // through iteration 1), then closes that iteration: MINLOC / termination, so a pair that stops
+            // leaves in the pass of its last iteration and its group is idle at the next refill
             T depth = 0;
             V3<T> n = zero3<T>();
             int r = ST_CONT;
-            if (!seeded) r = epa_close(c, S, depth, n);
+            if (!begun) r = epa_grow(c, S, seeded);
+            seeded = false;
+            begun = false;
+            if (r == ST_CONT) r = epa_close(c, S, depth, n);
             if constexpr ((PR & 1) != 0) {                 // park a polytope about to outgrow this tier
-                if (r == ST_CONT && !seeded && a.park && a.next_code >= 0) {
+                if (r == ST_CONT && a.park && a.next_code >= 0) {
                     const ParkCtl pk{a.park, a.park_ctr, a.park_cap, gjk_it,
                                      reinterpret_cast<uint32_t*>(a.out) + pair * (sizeof(T) == 8 ? 32 : 16)};
                     if (park_now(c, S, pk)) r = ST_PARKED;
                 }
             }
-            if (r == ST_CONT) r = epa_grow(c, S, seeded);
-            seeded = false;
             __builtin_amdgcn_wave_barrier();
             if (r != ST_CONT) {
                 finish(r, depth, n);

@@ -1,0 +1,57 @@
+#!/usr/bin/env python3
+"""Pass model of the refill EPA tiers (epa_kernel_refill, DESIGN.md §4.2 "Refill"), numpy only: no GPU and
+no library.  One wave of NG groups takes the pairs of a fixture in order; at the top of a pass the idle
+groups are refilled once at least REFILL of them are idle (or all are); every pass costs the same.  A pair
+of k EPA iterations (the oracle records' diag word) holds its group for k + 1 passes under the old exit
+rule (the close of iteration k ran alone in the pass after it) and for k under the shipped one (the close
+runs in the pass of its iteration).  Prints group-passes per pair (NG x wave passes / pairs: occupancy plus
+the passes a group waits idle for the refill threshold) under both rules.
+usage: python tools/refill_model.py [fixture.npz] [--tile 16] [--seed 0] [--cases 4/2,4/1,2/1]"""
+import argparse
+import os
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def wave_passes(life, ng, refill):
+    """Passes one wave of `ng` groups needs for pairs that hold a group for life[i] passes each."""
+    left = np.zeros(ng, np.int64)                           # passes the group's pair still needs
+    nxt, n, passes = 0, len(life), 0
+    while True:
+        idle = left == 0
+        if nxt < n and (idle.sum() >= refill or idle.all()):
+            for g in np.nonzero(idle)[0]:
+                if nxt < n:
+                    left[g] = life[nxt]
+                    nxt += 1
+        if not left.any():
+            return passes
+        passes += 1
+        left[left > 0] -= 1
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("fixture", nargs="?", default=os.path.join(ROOT, "tests", "golden", "c2_32v.npz"))
+    ap.add_argument("--tile", type=int, default=16, help="repeat the fixture's pairs this many times")
+    ap.add_argument("--seed", type=int, default=0, help="shuffle seed")
+    ap.add_argument("--cases", default="4/2,4/1,2/1", help="groups per wave / REFILL, comma list")
+    a = ap.parse_args()
+    rec = np.load(a.fixture)["rec_v2"]                      # REC64 bytes: collision at 104, diag word at 108
+    hit = rec[:, 104] != 0
+    iters = ((rec[:, 108:112].copy().view("<u4")[:, 0] >> 8) & 0xFF)[hit].astype(np.int64)
+    iters = iters[iters > 0]                                # pairs that ran EPA
+    print(f"{os.path.basename(a.fixture)}: {len(iters)} EPA pairs, mean {iters.mean():.2f} iterations, max {iters.max()}; "
+          f"tiled {a.tile}x, shuffled (seed {a.seed})")
+    life = np.random.default_rng(a.seed).permutation(np.tile(iters, a.tile))
+    print("groups/REFILL  group-passes per pair: close in the next pass | in the iteration's pass   wave passes")
+    for case in a.cases.split(","):
+        ng, refill = (int(x) for x in case.split("/"))
+        old, new = wave_passes(life + 1, ng, refill), wave_passes(life, ng, refill)
+        print(f"{ng} / {refill}          {ng * old / len(life):26.2f} | {ng * new / len(life):<26.2f} {100.0 * (new - old) / old:+.1f}%")
+
+
+if __name__ == "__main__":
+    main()
