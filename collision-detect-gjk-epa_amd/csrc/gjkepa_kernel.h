@@ -182,6 +182,19 @@
 #ifndef GJKEPA_CT_QUEUE04
 #define GJKEPA_CT_QUEUE04 1
 #endif
+// GJK tier 0 (16 groups per wave): once at most this many groups of a round are still in the tetrahedron
+// loop, they leave it for a per-wave LDS queue and a round of their own continues them when 16 are
+// pending (gjkepa_kernel.hip, gjk_kernel "Pending loop queue").  0: every pair finishes in its main round.
+// A/B r15 (profiles/r15/ab_gjk_queue.txt, GJK tier 0's launch on C2, parent 975 us): 6 / 7 / 8 845 / 841 /
+// 846 us, 10 880, 12 922; the pass model (tools/gjk_queue_model.py) puts the minimum at 6-7.
+#ifndef GJKEPA_G0_DEFER_AT
+#define GJKEPA_G0_DEFER_AT 7
+#endif
+// 1: a full round of queued pairs pushes its own last GJKEPA_G0_DEFER_AT groups back onto the queue.
+// A/B r15: 849 us against 841 without (the pairs pushed back pay the hull reload a second time).
+#ifndef GJKEPA_G0_REPUSH
+#define GJKEPA_G0_REPUSH 0
+#endif
 // Seed hand-over (fp64 compute only).  A GJK hit from the tetrahedron code leaves, beside the simplex
 // codes, the four unit face normals of its final simplex in the pair's record slot, and a flag that
 // says whether EPA may take them:
@@ -270,6 +283,8 @@
 // seeded from GJK's handed normals, and fresh pairs it seeded by its own arithmetic
 #define GJKEPA_TALLY_SEED_OWN 0x2D
 #define GJKEPA_TALLY_SEED_HANDED 0x2F
+// and one more: pairs GJK tier 0 finished in a round of queued pairs (GJKEPA_G0_DEFER_AT)
+#define GJKEPA_TALLY_GJK_QUEUED 0x2C
 
 // Polytope parking.  EPA tiers 2 and 3 hand a pair whose polytope is about to outgrow them to tier 4
 // with its polytope instead of its GJK simplex: the state at the start of an iteration (vertices,

@@ -1665,15 +1665,44 @@ CTX_T DEV bool warm_start(CTX& c, const uint32_t* w, uint32_t* kc) {
     return true;
 }
 
-// Sphere pre-test + GJK.  Returns PH_MISS, PH_HIT (codes k0..k3 filled) or an error status.  With `so`
-// (seed hand-over), a hit also returns this quad lane's face normal of the final simplex and whether
-// EPA may seed from the quad's normals.
-CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, SeedOut<T>* so = nullptr) {
+// The GJK phase (gjk_phase below) can leave its tetrahedron loop undecided and be entered again there: GJK
+// tier 0 moves a pair's loop from one round to another this way (gjk_kernel, "Pending loop queue").
+constexpr int PH_STOP = -3;      // GJK_STOPS: stopped by the wave with the pair undecided
+constexpr int GJK_STOPS = 1;     // MODE bit: after an iteration that decided nothing, stop (PH_STOP, *st filled) once at
+                                 // most defer_at groups of the wave are still in the loop
+constexpr int GJK_RESUMES = 2;   // MODE bit: no pre-test and no initial simplex; the loop goes on from *st
+struct GjkStop {
+    uint32_t k[4];               // the simplex's vertex codes
+    uint64_t hk1, hk2;           // cycle history: the two previous simplices' codes (codes_pack)
+    int it;                      // loop iterations done
+};
+// Four vertex codes in 64 bits (16 bits each: both indices are below 255 in the tiers that stop the loop;
+// kStale stays all ones).
+DEV uint64_t codes_pack(uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3) {
+    auto h = [](uint32_t k) { return (k & 0xffu) | ((k >> 8) & 0xff00u); };
+    return (uint64_t)(h(k0) | (h(k1) << 16)) | ((uint64_t)(h(k2) | (h(k3) << 16)) << 32);
+}
+DEV uint32_t codes_at(uint64_t p, int i) {
+    const uint32_t h = (uint32_t)(p >> (16 * i)) & 0xffffu;
+    return h == 0xffffu ? kStale : (h & 0xffu) | ((h >> 8) << 16);
+}
+
+// Sphere pre-test + GJK.  Returns PH_MISS, PH_HIT (codes k0..k3 filled), an error status or (GJK_STOPS)
+// PH_STOP.  With `so` (seed hand-over), a hit also returns this quad lane's face normal of the final simplex
+// and whether EPA may seed from the quad's normals.  A GJK_RESUMES call continues a stopped pair at iteration
+// st->it + 1 as if the loop had never been left: the simplex and the history are rebuilt from their codes,
+// the face normal with quad_normal as the iteration that stopped computed it.
+// The MODE bits only add statements or switch them off where they stand: no statement of the plain form
+// moves to another scope, which keeps the code of every kernel that calls the plain form what it was.
+template <int MODE = 0, typename T, typename TH, int G, int K, int VC, int FC, int LH>
+DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, SeedOut<T>* so = nullptr, [[maybe_unused]] GjkStop* st = nullptr,
+              [[maybe_unused]] int defer_at = 0) {
+    constexpr bool FRESH = (MODE & GJK_RESUMES) == 0;
     const V3<T> O = zero3<T>();
     auto& L = c.L;
     const int gl = c.g.gl;
     gjk_it = 0;
-    {   // RoughCollisionDetection_SphericalEnvelope (:1165-1188)
+    if constexpr (FRESH) {   // RoughCollisionDetection_SphericalEnvelope (:1165-1188)
         // the six sequential coordinate sums run on group lanes (sum j on lane j % G: hull j/3, axis j%3)
         T cs[(6 + G - 1) / G];           // centroid coordinate j0 + gl of pass j0 / G (hull j / 3, axis j % 3)
 #pragma unroll
@@ -1722,7 +1751,7 @@ CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, SeedOut<T>* so = null
     V3<T> s0 = O, s1 = O, s2 = O, s3 = O;   // fresh SAVE state: stale row 4 = 0
     uint32_t k0 = kStale, k1 = kStale, k2 = kStale, k3 = kStale;
     V3<T> dir;
-    for (int iter = 1;; ++iter) {
+    for (int iter = 1; FRESH; ++iter) {
         if (iter > 99) return PH_MISS;
         dir = vmk<T>((T)kDirTab[iter - 1][0], (T)kDirTab[iter - 1][1], (T)kDirTab[iter - 1][2]);
         s0 = support_pt(c, dir, k0);
@@ -1730,18 +1759,25 @@ CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, SeedOut<T>* so = null
         s1 = support_pt(c, dir, k1);
         if (!c.g.unib(allclose8(s0, s1))) break;
     }
-    dir = vec_pl(O, s0, s1);
-    s2 = support_pt(c, dir, k2);
-    if (c.g.unib(allclose8(s2, s0) || allclose8(s2, s1))) return PH_MISS;
-    dir = utzvec(cross(vsub(s1, s0), vsub(s2, s1)));
-    const T vd = dot(vsub(O, s2), dir);
+    if constexpr (FRESH) {
+        dir = vec_pl(O, s0, s1);
+        s2 = support_pt(c, dir, k2);
+        if (c.g.unib(allclose8(s2, s0) || allclose8(s2, s1))) return PH_MISS;
+        dir = utzvec(cross(vsub(s1, s0), vsub(s2, s1)));
+    }
+    const T vd = FRESH ? dot(vsub(O, s2), dir) : T(0);
     bool enter = false;
-    if (c.g.unib(fabs(vd) < Tol<T>::PT) && c.g.unib(inside_tri(s0, s1, s2, O))) enter = true;
+    if (FRESH && c.g.unib(fabs(vd) < Tol<T>::PT) && c.g.unib(inside_tri(s0, s1, s2, O))) enter = true;
     const bool tri = enter;  // hit on the initial triangle: no fourth point, no face normals
     const int q = gl & 3;
     V3<T> nq = zero3<T>();   // this quad lane's raw face normal of the current simplex
     T mdq = 0;
-    if (!enter) {
+    if constexpr (!FRESH) {
+        k0 = st->k[0]; k1 = st->k[1]; k2 = st->k[2]; k3 = st->k[3];
+        s0 = decode_pt(c, k0); s1 = decode_pt(c, k1); s2 = decode_pt(c, k2); s3 = decode_pt(c, k3);
+        nq = quad_normal(q, s0, s1, s2, s3, mdq);
+    }
+    if (FRESH && !enter) {
         if (c.g.unib(vd < T(0))) dir = vneg(dir);
         s3 = support_pt(c, dir, k3);
         const V3<T> n = uninml(s0, s1, s2);                         // DIST_PF_SIGN (:157)
@@ -1758,9 +1794,25 @@ CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, SeedOut<T>* so = null
         T h1[HS], h2[HS];
 #pragma unroll
         for (int t = 0; t < HS; ++t) { h1[t] = 0; h2[t] = 0; }
+        [[maybe_unused]] uint64_t hk1 = ~0ull, hk2 = ~0ull;   // GJK_STOPS: the history as codes (fresh: two zero simplices)
+        if constexpr (!FRESH) {
+            // the history's points are support points or the never-assigned zero row, and decode_pt is
+            // support_pt's expression: the same bits
+            hk1 = st->hk1; hk2 = st->hk2;
+            const V3<T> a0 = decode_pt(c, codes_at(hk1, 0)), a1 = decode_pt(c, codes_at(hk1, 1)),
+                        a2 = decode_pt(c, codes_at(hk1, 2)), a3 = decode_pt(c, codes_at(hk1, 3));
+            const V3<T> b0 = decode_pt(c, codes_at(hk2, 0)), b1 = decode_pt(c, codes_at(hk2, 1)),
+                        b2 = decode_pt(c, codes_at(hk2, 2)), b3 = decode_pt(c, codes_at(hk2, 3));
+#pragma unroll
+            for (int t = 0; t < HS; ++t) {
+                const int j = t * G + gl;
+                h1[t] = simplex_coord(j < 12 ? j : 0, a0, a1, a2, a3);
+                h2[t] = simplex_coord(j < 12 ? j : 0, b0, b1, b2, b3);
+            }
+        }
         const uint64_t lowg = G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull);
         const int sh = c.g.lane & ~(G - 1);
-        for (int it = 1;; ++it) {                                        // :182-236
+        for (int it = FRESH ? 1 : st->it + 1;; ++it) {                   // :182-236
             gjk_it = it;
             if (it > 50) return PH_MISS;
 #pragma unroll
@@ -1768,6 +1820,11 @@ CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, SeedOut<T>* so = null
                 const int j = t * G + gl;
                 h2[t] = h1[t];
                 h1[t] = simplex_coord(j < 12 ? j : 0, s0, s1, s2, s3);
+            }
+            if constexpr ((MODE & GJK_STOPS) != 0) {
+                static_assert(G * K < 255, "codes_pack keeps a vertex index in a byte");
+                hk2 = hk1;
+                hk1 = codes_pack(k0, k1, k2, k3);
             }
             GK_STAMP(SG_CHK);
             update_simplex_c(c, nq, s0, s1, s2, s3, k0, k1, k2, k3);
@@ -1793,6 +1850,15 @@ CTX_T DEV int gjk_phase(CTX& c, uint32_t* kc, int& gjk_it, SeedOut<T>* so = null
 #pragma unroll
             for (int p = 0; p < 4; ++p) over = over && (((e1 >> (3 * p)) & 7u) == 7u || ((e2 >> (3 * p)) & 7u) == 7u);
             if (c.g.unib(over)) return PH_MISS;
+            if constexpr ((MODE & GJK_STOPS) != 0) {
+                // the lanes that get here are the groups still in the loop, in step: the ballot counts them
+                if (popc(__ballot(true)) <= defer_at * G) {
+                    st->k[0] = k0; st->k[1] = k1; st->k[2] = k2; st->k[3] = k3;
+                    st->hk1 = hk1; st->hk2 = hk2;
+                    st->it = it;
+                    return PH_STOP;
+                }
+            }
         }
         GK_STAMP(SG_CHK);
     }
@@ -2124,10 +2190,163 @@ DEV void for_each_routed_pair(const Grp<G>& grp, int64_t n_pairs, const uint8_t*
     }
 }
 
+// What the GJK kernel leaves for a pair whose GJK phase returned r (PH_HIT, PH_MISS or an error status):
+// the warm slot, a hit's simplex codes and seed normals or the final record (o13: thirteen zeros).  Returns
+// the pair's route.  The one finish of every tier's main round and of tier 0's queued rounds.
+template <bool WARM, int G, typename T>
+DEV uint8_t gjk_finish(void* out, uint32_t* warm, int64_t pair, int gl, int na, int nb, int r, const uint32_t* kc,
+                       int gjk_it, const SeedOut<T>& so, const T* o13) {
+    uint8_t next = 0;
+    if (WARM && gl < 4)     // this call's simplex seeds the next call; a miss mark; none for errors
+        warm[4 * pair + gl] = r == PH_HIT ? (gl == 0 ? kc[0] : gl == 1 ? kc[1] : gl == 2 ? kc[2] : kc[3])
+                            : (r == PH_MISS && gl == 0) ? kWarmMiss : kStale;
+    if (r == PH_HIT) {
+#pragma unroll
+        for (int j0 = 0; j0 < 6; j0 += G) {   // simplex codes, GJK iterations, no parked polytope
+            const int j = j0 + gl;
+            const uint32_t word = j == 0 ? kc[0] : j == 1 ? kc[1] : j == 2 ? kc[2] : j == 3 ? kc[3] : j == 4 ? (uint32_t)gjk_it : 0u;
+            if (j < 6) reinterpret_cast<uint32_t*>(out)[pair * (sizeof(T) == 8 ? 32 : 16) + j] = word;
+        }
+        if constexpr (handoff<T>()) {
+            // the quad's normals in EPA seed order (GJK faces 0..3 are seed faces 1, 2, 0, 3) and
+            // the flag, for every hit: the slot may hold an earlier record's bytes
+            uint32_t* slot = reinterpret_cast<uint32_t*>(out) + pair * 32;
+            if (so.ok && gl < 4) {
+                const int f = gl == 0 ? 1 : gl == 1 ? 2 : gl == 2 ? 0 : 3;
+                T* np = reinterpret_cast<T*>(slot + kSeedNmlWord) + 3 * f;
+                np[0] = so.nq.x; np[1] = so.nq.y; np[2] = so.nq.z;
+            }
+            if (gl == 0) slot[kSeedFlagWord] = so.ok ? 1u : 0u;
+        }
+        next = (uint8_t)(GJKEPA_ROUTE_EPA0 + epa_tier_for(na > nb ? na : nb));
+    } else if (r == PH_MISS) {
+        store_record<G, T>(out, pair, gl, o13, 0, 0, 0, 0u);
+    } else if (certify<T>()) {                // fp32: GJK-phase error, recomputed in fp64
+        next = GJKEPA_ROUTE_REDO;
+    } else {                                  // GJK-phase error (reference would STOP)
+        store_record<G, T>(out, pair, gl, o13, 1, 0, r, (uint32_t)(gjk_it & 0xff));
+    }
+    return next;
+}
+
+// Pending loop queue (GJKEPA_G0_DEFER_AT; the tier with 16 groups per wave, tier 0, with fp32 vertex storage).  A wave stays in the
+// tetrahedron loop until its slowest group leaves: on C2 8.55 iterations per round for 3.34 of need (a hit
+// takes 1.8 on average, a miss, which has no separating-axis exit, 7.4).  Once at most GJKEPA_G0_DEFER_AT
+// groups of a main round are still in the loop, they leave it undecided and push onto a ring in the wave's
+// LDS, behind the 16 group images: the pair, its hulls' offsets and counts, the iterations done, the
+// simplex as four codes and the cycle history as twice four (GjkStop).  They touch neither record nor
+// route byte, tally or warm slot.  Once 16 entries are pending, a round of their own continues them on all
+// groups: group g pops entry g, loads both hulls again (in L2), decodes the simplex and the history
+// (decode_pt: support_pt's expression), recomputes its face normal with quad_normal, goes on with the same
+// loop at the next iteration (so the 50-iteration cap and the iteration count are the reference's) and
+// runs the same finish.  GJKEPA_G0_REPUSH: such a round pushes its own last groups back.  The ring lives
+// across the wave's units; what is left when the wave has no further unit takes partial rounds that
+// run every pair to its end.  A main round meets at most 15 entries and adds at most 16, a queued round
+// takes 16 and adds at most 16: never more than 31 are held.
+struct PendGjkEntry {
+    int64_t pair, oa, ob;        // pair index; vertex offsets of hull A / B
+    uint64_t hk1, hk2;           // cycle history: the two previous simplices' codes (codes_pack)
+    uint32_t k[4];               // simplex codes
+    int32_t na, nb, it, pad;     // vertex counts; loop iterations done
+};
+template <int G> struct PendGjkQueue {
+    static constexpr int CAP = 2 * (64 / G);                      // ring slots (a power of two)
+    PendGjkEntry e[CAP];
+};
+// Only with fp32 vertex storage: the fp64-storage tier-0 kernels were at the register cap before (255 / 256 VGPRs,
+// 4 / 18 spilled) and with the queue spilled 35 / 52, with reloads inside the tetrahedron loop; they keep the
+// path without a queue.
+template <int G, typename TIn> constexpr bool gjk_queue() { return GJKEPA_G0_DEFER_AT > 0 && 64 / G >= 16 && sizeof(TIn) == 4; }
+template <typename TIn, typename T, int G, int K> constexpr size_t gjk_lds_bytes() {
+    size_t bytes = lds_stride<Lds<T, TIn, G, K, 0, 0>, G>() * (64 / G);       // the groups' images
+    if constexpr (gjk_queue<G, TIn>()) bytes += sizeof(PendGjkQueue<G>);           // then the ring
+    return bytes;
+}
+// The groups with `stopped` set push their entries behind the ring's `qn` pending ones, lowest group first;
+// returns how many pushed.  Every group that pushes in a round must reach the ballot together, since a
+// group's slot is its rank among them: a queued round calls this with the whole wave, the main round from
+// inside `if (r == PH_STOP)`, where that holds because a round has one wave-wide stop (gjk_phase's ballot
+// makes every group still in the loop leave in the same iteration) and the stopped groups reconverge behind
+// the inlined gjk_phase.  `qn` is the count from before the round, the same for all of them; the caller adds
+// the pushes afterwards (the main round in its `after` hook).
+template <int G>
+DEV int gjk_queue_push(PendGjkQueue<G>& Q, int qhead, int qn, const Grp<G>& grp, bool stopped, int64_t pair, int64_t oa,
+                       int64_t ob, int na, int nb, const GjkStop& st) {
+    const uint64_t pushing = __ballot(stopped);
+    if (stopped && grp.gl == 0) {
+        const int rank = popc(pushing & ((1ull << grp.lane) - 1ull)) / G;
+        auto& e = Q.e[(qhead + qn + rank) & (PendGjkQueue<G>::CAP - 1)];
+        e.pair = pair; e.oa = oa; e.ob = ob;
+        e.hk1 = st.hk1; e.hk2 = st.hk2;
+        e.k[0] = st.k[0]; e.k[1] = st.k[1]; e.k[2] = st.k[2]; e.k[3] = st.k[3];
+        e.na = na; e.nb = nb; e.it = st.it; e.pad = 0;
+    }
+    __builtin_amdgcn_wave_barrier();
+    return popc(pushing) / G;
+}
+
+// One round of queued pairs: group g takes pending entry g of the ring from `qhead` on (g < cnt <= 64 / G;
+// qn entries are pending in all).  defer_at > 0 (GJKEPA_G0_REPUSH): its last groups push back; returns how
+// many did.  Inlined at its uses, unlike case04_round: as a function of its own, the values the kernel keeps
+// across the call had to sit in the callee-saved registers, which cost the fp32-storage fp64 kernel 10
+// spilled VGPRs with reloads inside the tetrahedron loop (256 VGPRs; GJK tier 0 on C2 975 -> 895 us);
+// inlined it has none (248 VGPRs; 841 us).
+template <typename TIn, typename T, int G, int K, bool LH, bool WARM>
+DEV int gjk_queue_round(int qhead, int cnt, int qn, int defer_at, const TIn* verts, void* out, uint8_t* route,
+                        uint32_t* warm) {
+    using L_t = Lds<T, TIn, G, K, 0, 0>;
+    using Q_t = PendGjkQueue<G>;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const Grp<G> grp;
+    const int gl = grp.gl, g = grp.lane / G;
+    L_t& L = *reinterpret_cast<L_t*>(smem + lds_stride<L_t, G>() * g);
+    Q_t& Q = *reinterpret_cast<Q_t*>(smem + lds_stride<L_t, G>() * (64 / G));
+    // the entry into registers before any group of this round pushes: a push may take a slot this round frees
+    int64_t pair = 0, oa = 0, ob = 0;
+    int na = 0, nb = 0;
+    GjkStop st{{kStale, kStale, kStale, kStale}, ~0ull, ~0ull, 0};
+    if (g < cnt) {
+        const auto& e = Q.e[(qhead + g) & (Q_t::CAP - 1)];
+        pair = e.pair; oa = e.oa; ob = e.ob;
+        st.hk1 = e.hk1; st.hk2 = e.hk2;
+        st.k[0] = e.k[0]; st.k[1] = e.k[1]; st.k[2] = e.k[2]; st.k[3] = e.k[3];
+        na = e.na; nb = e.nb; st.it = e.it;
+    }
+    __builtin_amdgcn_wave_barrier();
+    bool stopped = false;
+    if (g < cnt) {
+        Ctx<T, TIn, G, K, 0, 0, LH> c{L, grp};
+        c.na = na;
+        c.nb = nb;
+        load_hulls(c, verts + oa, verts + ob);
+        GK_STAMP(SG_LOAD);
+        uint32_t kc[4];
+        int gjk_it = 0;
+        SeedOut<T> so{zero3<T>(), false};
+        const int r = gjk_phase<GJK_RESUMES | (GJKEPA_G0_REPUSH != 0 ? GJK_STOPS : 0)>(c, kc, gjk_it, &so, &st, defer_at);
+        stopped = r == PH_STOP;
+        if (!stopped) {
+            __builtin_amdgcn_wave_barrier();
+            T o13[13];
+#pragma unroll
+            for (int i = 0; i < 13; ++i) o13[i] = T(0);
+            const uint8_t next = gjk_finish<WARM, G, T>(out, warm, pair, gl, na, nb, r, kc, gjk_it, so, o13);
+            if (gl == 0) { route[pair] = next; tally_route(next); tally_route(GJKEPA_TALLY_GJK_QUEUED); }
+        }
+    }
+    int pushed = 0;
+    if constexpr (GJKEPA_G0_REPUSH != 0) pushed = gjk_queue_push<G>(Q, qhead, qn, grp, stopped, pair, oa, ob, na, nb, st);
+    __builtin_amdgcn_wave_barrier();
+    return pushed;
+}
+
 // GJK kernel: sphere pre-test + GJK.  Misses and errors get their final record here; hits park the
 // simplex codes (5 words) in their own record slot and are routed to the smallest EPA tier that
 // holds their hulls.  Tier 0 takes every pair; hulls above its capacity are routed to tier 1.
 // WARM instantiations serve gjkepa_batch_warm_device (a.warm set); the plain ones carry no warm code.
+// QG (tier 0 with fp32 vertex storage, "Pending loop queue" above): a group whose loop the wave stopped pushes
+// its entry and leaves everything else to its queued round.  The additions are discarded statements in the
+// kernels without a queue.
 template <typename TIn, typename T, int G, int K, int MINW, bool LH, bool WARM>
 __global__ __launch_bounds__(64, MINW) void gjk_kernel(const gjkepa_gjk_args a) {
     static_assert(G >= 4, "the tetrahedron faces run on quads");
@@ -2142,6 +2361,12 @@ __global__ __launch_bounds__(64, MINW) void gjk_kernel(const gjkepa_gjk_args a) 
     if (tier_empty(a.tally, a.route_code)) return;
     tally_begin();
     const int claim = pick_claim(a.tally, a.route_code, a.n_pairs, a.claim);
+    constexpr bool QG = gjk_queue<G, TIn>();
+    constexpr int GPW = 64 / G;
+    using Q_t = PendGjkQueue<G>;
+    static_assert(lds_stride<L_t, G>() % 8 == 0, "the ring follows the images, 8-byte aligned");
+    [[maybe_unused]] int qhead = 0, qn = 0;    // QG, wave-uniform: first pending slot, entries pending
+    [[maybe_unused]] bool pushed = false;      // QG: this group pushed an entry in the current main round
     auto body = [&](int64_t pair, const PairMeta& pm) {
         GK_STAMP(SG_ROUTE);
         Ctx<T, TIn, G, K, 0, 0, LH> c{L, grp};
@@ -2172,45 +2397,46 @@ __global__ __launch_bounds__(64, MINW) void gjk_kernel(const gjkepa_gjk_args a) 
                     if (a.warm[4 * pair] != kWarmMiss) warm_hit = warm_start(c, a.warm + 4 * pair, kc);
                 }
                 SeedOut<T> so{zero3<T>(), false};     // a warm-start hit hands nothing over
+                [[maybe_unused]] GjkStop st;          // QG: the loop's state when the wave stopped it
                 if (warm_hit) r = PH_HIT;
+                else if constexpr (QG) r = gjk_phase<GJK_STOPS>(c, kc, gjk_it, &so, &st, GJKEPA_G0_DEFER_AT);
                 else r = gjk_phase(c, kc, gjk_it, &so);
                 __builtin_amdgcn_wave_barrier();
                 GK_STAMP(SG_CHK);
-                if (WARM && gl < 4)     // this call's simplex seeds the next call; a miss mark; none for errors
-                    a.warm[4 * pair + gl] = r == PH_HIT ? (gl == 0 ? kc[0] : gl == 1 ? kc[1] : gl == 2 ? kc[2] : kc[3])
-                                          : (r == PH_MISS && gl == 0) ? kWarmMiss : kStale;
-                if (r == PH_HIT) {
-#pragma unroll
-                    for (int j0 = 0; j0 < 6; j0 += G) {   // simplex codes, GJK iterations, no parked polytope
-                        const int j = j0 + gl;
-                        const uint32_t word = j == 0 ? kc[0] : j == 1 ? kc[1] : j == 2 ? kc[2] : j == 3 ? kc[3] : j == 4 ? (uint32_t)gjk_it : 0u;
-                        if (j < 6) reinterpret_cast<uint32_t*>(a.out)[pair * (sizeof(T) == 8 ? 32 : 16) + j] = word;
+                if constexpr (QG) {
+                    if (r == PH_STOP) {                   // its queued round finishes the pair
+                        Q_t& Q = *reinterpret_cast<Q_t*>(smem + lds_stride<L_t, G>() * GPW);
+                        gjk_queue_push<G>(Q, qhead, qn, grp, true, pair, pm.oa, pm.ob, na, nb, st);
+                        pushed = true;
+                        GK_STAMP(SG_STORE);
+                        return;
                     }
-                    if constexpr (handoff<T>()) {
-                        // the quad's normals in EPA seed order (GJK faces 0..3 are seed faces 1, 2, 0, 3) and
-                        // the flag, for every hit: the slot may hold an earlier record's bytes
-                        uint32_t* slot = reinterpret_cast<uint32_t*>(a.out) + pair * 32;
-                        if (so.ok && gl < 4) {
-                            const int f = gl == 0 ? 1 : gl == 1 ? 2 : gl == 2 ? 0 : 3;
-                            T* np = reinterpret_cast<T*>(slot + kSeedNmlWord) + 3 * f;
-                            np[0] = so.nq.x; np[1] = so.nq.y; np[2] = so.nq.z;
-                        }
-                        if (gl == 0) slot[kSeedFlagWord] = so.ok ? 1u : 0u;
-                    }
-                    next = (uint8_t)(GJKEPA_ROUTE_EPA0 + epa_tier_for(na > nb ? na : nb));
-                } else if (r == PH_MISS) {
-                    store_record<G, T>(a.out, pair, gl, o13, 0, 0, 0, 0u);
-                } else if (certify<T>()) {                // fp32: GJK-phase error, recomputed in fp64
-                    next = GJKEPA_ROUTE_REDO;
-                } else {                                  // GJK-phase error (reference would STOP)
-                    store_record<G, T>(a.out, pair, gl, o13, 1, 0, r, (uint32_t)(gjk_it & 0xff));
                 }
+                next = gjk_finish<WARM, G, T>(a.out, a.warm, pair, gl, na, nb, r, kc, gjk_it, so, o13);
             }
         }
         if (gl == 0) { a.route[pair] = next; tally_route(next); }
         __builtin_amdgcn_wave_barrier();
         GK_STAMP(SG_STORE);
     };
+    if constexpr (QG) {
+        auto rounds = [&](int defer_at) __attribute__((always_inline)) {
+            const int cnt = qn < GPW ? qn : GPW;
+            const int back = gjk_queue_round<TIn, T, G, K, LH, WARM>(qhead, cnt, qn, defer_at, verts, a.out, a.route, a.warm);
+            qhead = (qhead + cnt) & (Q_t::CAP - 1);
+            qn += __builtin_amdgcn_readfirstlane(back) - cnt;
+            GK_STAMP(SG_STORE);
+        };
+        auto after = [&]() __attribute__((always_inline)) {   // per main round: count the pushes, run full rounds
+            qn += popc(__ballot(pushed)) / G;
+            pushed = false;
+            while (qn >= GPW) rounds(GJKEPA_G0_REPUSH != 0 ? GJKEPA_G0_DEFER_AT : 0);
+        };
+        for_each_routed_pair<G, true>(grp, a.n_pairs, a.route, a.route_code, a.ctr, claim, false, body, a.pairs, a.hull_cnt,
+                                      a.hull_off, after);
+        GK_STAMP(SG_ROUTE);
+        while (qn > 0) rounds(0);        // no further unit: partial rounds that push nothing back
+    } else
     for_each_routed_pair<G, true>(grp, a.n_pairs, a.route, a.route_code, a.ctr, claim, false, body, a.pairs, a.hull_cnt,
                                   a.hull_off);
     GK_STAMP(SG_ROUTE);
@@ -3293,8 +3519,7 @@ template <typename K_t> int grid_for(K_t kfn, size_t lds, int num_cus, int grid)
 template <typename TIn, typename T, int G, int K, int MINW, bool LH>
 hipError_t launch_gjk(const gjkepa_gjk_args& a, hipStream_t s) {
     auto kfn = a.warm ? gk::gjk_kernel<TIn, T, G, K, MINW, LH, true> : gk::gjk_kernel<TIn, T, G, K, MINW, LH, false>;
-    constexpr int GPW = 64 / G;
-    const size_t lds = gk::lds_stride<gk::Lds<T, TIn, G, K, 0, 0>, G>() * GPW;
+    const size_t lds = gk::gjk_lds_bytes<TIn, T, G, K>();         // the groups' images, then tier 0's pending ring
     int grid = grid_for(kfn, lds, a.num_cus, a.grid);
     grid = grid_cap<G>(a.n_pairs, grid);
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(64), lds, s, a);
