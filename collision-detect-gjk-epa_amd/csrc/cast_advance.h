@@ -11,9 +11,11 @@
 // translation moves every point of it alike.
 //
 // Host and device code like dist_simplex.h (plain fp64, no FMA contraction): the cast kernel
-// (gjkepa_kernel.hip, part 13) and tests/cast_host.cpp run this text.  Linear motion only.
+// (gjkepa_kernel.hip, part 13) and tests/cast_host.cpp run this text.  Linear motion only; the cast under
+// a rigid motion of both hulls (cast_advance_rigid, below) is gjkepa_cast_rigid_batch's.
 #pragma once
 #include "dist_simplex.h"
+#include "rigid_pose.h"
 
 namespace gkd {
 
@@ -99,6 +101,65 @@ DS_HD void cast_record(const CastResult& c, const Simplex& s, D3 d, At&& at, Bt&
     o13[1] = pa.x; o13[2] = pa.y; o13[3] = pa.z;
     o13[4] = pb.x; o13[5] = pb.y; o13[6] = pb.z;
     if (len > 0.0) { o13[7] = e.x / len; o13[8] = e.y / len; o13[9] = e.z / len; }
+}
+
+// ---- the cast under a rigid motion of both hulls (gjkepa_cast_rigid_batch, rigid_pose.h) ---------------
+// Hull A moves by ma and hull B by mb, each about its own pivot.  At every visited time the distance GJK
+// runs on the posed hulls A(t), B(t); the simplex is carried by its codes, and since the points of a
+// carried simplex move apart under rotation it is only a valid start: dist_gjk_from reduces it from
+// scratch.  Along the fixed unit normal n (from B to A) a vertex x of body X moves at
+// n.v_X + theta'(t) (x(t) - c_X(t)).(n x k_X), k_X = w_X / |w_X|, and theta' <= |w_X|, so with
+// rho_X = max_i |x_i - c_X| the support gap lb along n shrinks at most at the rate
+//     s = n.(v_B - v_A) + |n x w_A| rho_A + |n x w_B| rho_B
+// (a spin about n costs nothing).  After dt = (lb - tau / 2) / s the gap is still tau / 2.  s <= 0, or a
+// step that reaches t = 1, proves a miss with n the normal of a plane that separates the posed hulls at
+// t = 1.  Convergence under spin is linear, so the step cap is flat.
+constexpr int kCastRigidMaxSteps = 64;
+
+// sup(dir, ia, ib): first-maximum supports of the posed hulls along dir / -dir, as indices of the unposed
+// vertices; pt(ia, ib) = a_ia(t) - b_ib(t) at the time on_t was last called with; on_t(t): t has changed
+// (called with 0 before the first distance run).  On IMPACT and a separated START s holds the final
+// simplex, and the last time given to on_t is toi.
+template <typename Sup, typename Pt, typename OnT, typename Sqrt>
+DS_HD CastResult cast_advance_rigid(Simplex& s, const Motion& ma, const Motion& mb, double rho_a, double rho_b, double tau,
+                                    Sup&& sup, Pt&& pt, OnT&& on_t, Sqrt&& sqrt_) {
+    CastResult c;
+    c.outcome = CAST_STOPPED;
+    c.steps = 0;
+    c.iters = 0u;
+    c.n = mk(0.0, 0.0, 0.0);
+    double t = 0.0;
+    on_t(t);
+    for (;;) {
+        const Result r = dist_gjk_from(s, c.steps > 0, __builtin_huge_val(), sup, pt, sqrt_);
+        c.iters += (uint32_t)r.iters;
+        if (r.outcome == DIST_OVERLAP) { if (c.steps == 0) c.outcome = CAST_START_OVERLAP; break; }
+        if (r.outcome != DIST_SEPARATED) break;
+        const D3 w = closest(s);
+        if (sqrt_(dot(w, w)) <= tau) { c.outcome = c.steps == 0 ? CAST_START : CAST_IMPACT; break; }
+        const double vn = sqrt_(dot(r.v, r.v));
+        const D3 n = mk(r.v.x / vn, r.v.y / vn, r.v.z / vn);
+        const D3 xa = cross(n, ma.w), xb = cross(n, mb.w);
+        const double sd = dot(n, sub(mb.v, ma.v)) + sqrt_(dot(xa, xa)) * rho_a + sqrt_(dot(xb, xb)) * rho_b;
+        if (!(sd > 0.0)) { c.outcome = CAST_MISS; c.n = n; break; }
+        const double dt = (r.lower - 0.5 * tau) / sd;
+        if (!(t + dt > t)) break;                      // no progress
+        if (t + dt >= 1.0) { c.outcome = CAST_MISS; c.n = n; break; }
+        t += dt;
+        on_t(t);
+        c.steps += 1;
+        if (c.steps >= kCastRigidMaxSteps) break;
+    }
+    c.toi = c.outcome == CAST_MISS ? 1.0 : t;
+    return c;
+}
+
+// cast_record for the rigid cast.  at(i), bt(i): vertex i of hull A / hull B posed at toi; both witness
+// points are sums of posed vertices, so nothing is moved afterwards.
+template <typename At, typename Bt, typename Sqrt>
+DS_HD void cast_record_rigid(const CastResult& c, const Simplex& s, At&& at, Bt&& bt, Sqrt&& sqrt_, double* o13,
+                             uint32_t* code, int& n, int& status, int& flags) {
+    cast_record(c, s, mk(0.0, 0.0, 0.0), at, bt, sqrt_, o13, code, n, status, flags);
 }
 
 }  // namespace gkd

@@ -11,7 +11,8 @@
 // same pattern for the batched convex-hull kernels (two tiers over one cloud list), and
 // gjkepa_distance_batch(_device) for the separation-distance tiers (a counter reset and three launches on
 // the caller's stream, counters in a workspace of their own), and gjkepa_cast_batch(_device) and
-// gjkepa_manifold_batch(_device) for the linear-cast and the contact-manifold tiers (the same chain shape).
+// gjkepa_manifold_batch(_device) for the linear-cast and the contact-manifold tiers (the same chain shape), as
+// does gjkepa_cast_rigid_batch(_device) for the rigid-motion cast; gjkepa_pose_pool(_device) is one launch.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -31,6 +32,7 @@
 #include "hull_kernel.h"
 #include "broadphase_kernel.h"
 #include "contacts_kernel.h"
+#include "pose_kernel.h"
 #include "capi_internal.h"
 
 namespace {
@@ -102,7 +104,8 @@ struct DeviceState {
     DevBuf c_idx, c_hits, c_ws, c_n;                        // gjkepa_collide staging
     DevBuf q_blk, q_ws;                                     // combined gjkepa_query batches
     DevBuf d_rec, d_out, d_ws;                              // gjkepa_distance_batch / gjkepa_cast_batch staging
-    DevBuf d_motion;                                        // gjkepa_cast_batch staging
+    DevBuf d_motion;                                        // gjkepa_cast_batch / gjkepa_cast_rigid_batch / gjkepa_pose_pool staging
+    DevBuf d_time, d_status;                                // gjkepa_pose_pool staging
     HostBuf q_host;
 };
 
@@ -902,6 +905,127 @@ int gjkepa_cast_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scal
                            tolerance)))
         return rc;
     st.down(out, d->d_out, (size_t)n_pairs * sizeof(gjkepa_cast_f64));
+    st.sync();
+    return st.failed();
+}
+
+// ---- rigid-motion cast ---------------------------------------------------------------------------
+int64_t gjkepa_cast_rigid_workspace_bytes(int64_t n_pairs) { return gjkepa_cast_workspace_bytes(n_pairs); }
+
+}  // extern "C"
+
+namespace {
+int cast_rigid_enqueue(const PairQuery& q, const double* body_motion, double tolerance) {
+    gjkepa_cast_rigid_args a{};
+    a.body_motion = body_motion;
+    a.tolerance = tolerance;
+    return pair_query_enqueue(a, q, "rigid cast", gjkepa_launch_cast_rigid);
+}
+}  // namespace
+
+extern "C" {
+
+int gjkepa_cast_rigid_batch_device(int32_t vert_dtype, const void* verts, const int64_t* hull_off,
+                                   const int32_t* hull_cnt, const int32_t* pairs, int64_t n_pairs,
+                                   const double* body_motion, double tolerance, const void* records,
+                                   int32_t records_precision, void* out, void* workspace, int64_t workspace_bytes,
+                                   void* stream) {
+    const gjkepa_internal::Range range_("gjkepa_cast_rigid_batch_device (chain enqueue)");
+    int rc = cast_args_ok(vert_dtype, n_pairs, records, records_precision, tolerance);
+    if (rc) return rc;
+    if (n_pairs > 0 && (!verts || !hull_off || !hull_cnt || !pairs || !body_motion || !out || !workspace))
+        return fail(GJKEPA_E_ARG, "null pointer");
+    if (n_pairs == 0) return 0;
+    return cast_rigid_enqueue(PairQuery{vert_dtype, verts, hull_off, hull_cnt, pairs, n_pairs, records, records_precision, out,
+                                        workspace, workspace_bytes, (hipStream_t)stream, 0},
+                              body_motion, tolerance);
+}
+
+int gjkepa_cast_rigid_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
+                            const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                            const int32_t* pairs, int64_t n_pairs, const double* body_motion, double tolerance,
+                            const void* records, int32_t records_precision, void* out, int32_t device) {
+    const gjkepa_internal::Range range_("gjkepa_cast_rigid_batch (H2D, chain, D2H)");
+    if (n_hulls < 0 || n_vert_scalars < 0) return fail(GJKEPA_E_ARG, "bad sizes");
+    int rc = cast_args_ok(vert_dtype, n_pairs, records, records_precision, tolerance);
+    if (rc) return rc;
+    if (n_pairs == 0) return 0;
+    if (!verts || !hull_off || !hull_cnt || !pairs || !body_motion || !out) return fail(GJKEPA_E_ARG, "null pointer");
+    if ((rc = check_pool(pairs, n_pairs, hull_off, hull_cnt, n_hulls, n_vert_scalars, kAnyHullCount))) return rc;
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
+    st.up_pool(vert_dtype, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls, pairs, n_pairs);
+    st.up(d->d_motion, body_motion, (size_t)n_hulls * GJKEPA_MOTION_DOUBLES * sizeof(double));
+    st.up(d->d_rec, records, records ? (size_t)n_pairs * (size_t)gjkepa_record_bytes(records_precision) : 0);
+    st.room(d->d_out, (size_t)n_pairs * sizeof(gjkepa_cast_f64));
+    st.room(d->d_ws, (size_t)GJKEPA_CAST_WS_BYTES);
+    if ((rc = st.failed())) return rc;
+    if ((rc = cast_rigid_enqueue(staged_query(d, vert_dtype, n_pairs, records, records_precision),
+                                 d->d_motion.as<const double>(), tolerance)))
+        return rc;
+    st.down(out, d->d_out, (size_t)n_pairs * sizeof(gjkepa_cast_f64));
+    st.sync();
+    return st.failed();
+}
+
+}  // extern "C"
+
+namespace {
+// ---- pool pose -----------------------------------------------------------------------------------
+int pose_args_ok(int32_t in_dtype, const void* verts_in, const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                 const double* body_motion, int32_t out_dtype, const void* verts_out) {
+    if (n_hulls < 0 || (in_dtype != GJKEPA_DTYPE_F32 && in_dtype != GJKEPA_DTYPE_F64) ||
+        (out_dtype != GJKEPA_DTYPE_F32 && out_dtype != GJKEPA_DTYPE_F64))
+        return fail(GJKEPA_E_ARG, "bad n_hulls/dtype");
+    if (n_hulls > 0 && (!verts_in || !hull_off || !hull_cnt || !body_motion || !verts_out)) return fail(GJKEPA_E_ARG, "null pointer");
+    if (n_hulls > 0 && verts_in == verts_out && in_dtype != out_dtype)
+        return fail(GJKEPA_E_ARG, "in place needs equal dtypes");
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int gjkepa_pose_pool_device(int32_t in_dtype, const void* verts_in, const int64_t* hull_off, const int32_t* hull_cnt,
+                            int64_t n_hulls, const double* body_motion, const double* time, int32_t out_dtype,
+                            void* verts_out, int8_t* status, void* stream) {
+    const gjkepa_internal::Range range_("gjkepa_pose_pool_device (enqueue)");
+    int rc = pose_args_ok(in_dtype, verts_in, hull_off, hull_cnt, n_hulls, body_motion, out_dtype, verts_out);
+    if (rc || n_hulls == 0) return rc;
+    const gjkepa_pose_args a{verts_in, hull_off, hull_cnt, n_hulls, body_motion, time, verts_out, status};
+    const hipError_t e = gjkepa_launch_pose(in_dtype, out_dtype, a, num_cus_current(), (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "pose launch");
+}
+
+int gjkepa_pose_pool(int32_t in_dtype, const void* verts_in, int64_t n_vert_scalars, const int64_t* hull_off,
+                     const int32_t* hull_cnt, int64_t n_hulls, const double* body_motion, const double* time,
+                     int32_t out_dtype, void* verts_out, int8_t* status, int32_t device) {
+    const gjkepa_internal::Range range_("gjkepa_pose_pool (H2D, launch, D2H)");
+    if (n_vert_scalars < 0) return fail(GJKEPA_E_ARG, "bad sizes");
+    int rc = pose_args_ok(in_dtype, verts_in, hull_off, hull_cnt, n_hulls, body_motion, out_dtype, verts_out);
+    if (rc || n_hulls == 0) return rc;
+    if ((rc = check_pool(nullptr, 0, hull_off, hull_cnt, n_hulls, n_vert_scalars, GJKEPA_MAX_HULL_VERTS))) return rc;
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
+    const bool in_place = verts_in == verts_out;
+    const size_t out_bytes = (size_t)n_vert_scalars * (out_dtype == GJKEPA_DTYPE_F32 ? 4 : 8);
+    st.up_pool(in_dtype, verts_in, n_vert_scalars, hull_off, hull_cnt, n_hulls);
+    st.up(d->d_motion, body_motion, (size_t)n_hulls * GJKEPA_MOTION_DOUBLES * sizeof(double));
+    st.up(d->d_time, time, (size_t)n_hulls * sizeof(double));
+    // the scalars the kernel leaves alone (no hull's, a bad hull's) keep the caller's values
+    if (!in_place) st.up(d->d_out, verts_out, out_bytes);
+    if (status) st.room(d->d_status, (size_t)n_hulls);
+    if ((rc = st.failed())) return rc;
+    DevBuf& o = in_place ? d->verts : d->d_out;
+    const gjkepa_pose_args a{d->verts.p, d->off.as<const int64_t>(), d->cnt.as<const int32_t>(), n_hulls,
+                             d->d_motion.as<const double>(), time ? d->d_time.as<const double>() : nullptr, o.p,
+                             status ? d->d_status.as<int8_t>() : nullptr};
+    const hipError_t e = gjkepa_launch_pose(in_dtype, out_dtype, a, d->num_cus, d->stream);
+    if (e != hipSuccess) return hip_fail(e, "pose launch");
+    st.down(verts_out, o, out_bytes);
+    if (status) st.down(status, d->d_status, (size_t)n_hulls);
     st.sync();
     return st.failed();
 }

@@ -439,6 +439,37 @@ struct gjkepa_cast_args {
 };
 hipError_t gjkepa_launch_cast(int tier, int vert_dtype, const gjkepa_cast_args& a, hipStream_t s);
 
+// ---- rigid-motion cast (gjkepa_cast_rigid_batch_device): cast_advance_rigid (cast_advance.h) over the pose
+// of rigid_pose.h, on the linear cast's shapes, schedule, record and workspace layout.  The two bodies'
+// motions, the step's pose state and the two radii live in the group's LDS image beside the hulls.
+#ifndef GJKEPA_R0_MINW
+#define GJKEPA_R0_MINW 2        // waves per SIMD of the rigid cast tiers
+#endif
+#ifndef GJKEPA_R1_MINW
+#define GJKEPA_R1_MINW 2
+#endif
+#ifndef GJKEPA_R2_MINW
+#define GJKEPA_R2_MINW 2
+#endif
+struct gjkepa_cast_rigid_args {
+    const void* verts;
+    const int64_t* hull_off;
+    const int32_t* hull_cnt;
+    const int32_t* pairs;
+    int64_t n_pairs;
+    const unsigned char* records;   // optional contact records (nullptr: none)
+    int rec_stride;
+    int rec_hit_off;
+    const double* body_motion;      // GJKEPA_MOTION_DOUBLES per hull of the pool: v, w, c
+    double tolerance;               // the cast stops within this distance (finite, > 0)
+    uint32_t* ctr;                  // this launch's chunk counter (zero at launch)
+    void* out;                      // gjkepa_cast_f64 records
+    int grid;                       // <= 0: occupancy x CUs
+    int num_cus;
+    static constexpr int kSkipFlag = GJKEPA_CAST_SKIPPED;
+};
+hipError_t gjkepa_launch_cast_rigid(int tier, int vert_dtype, const gjkepa_cast_rigid_args& a, hipStream_t s);
+
 // ---- contact manifold (gjkepa_manifold_batch_device): one pass over the two hulls of every pair the
 // contact records call a collision, on the distance tiers' shapes, pair schedule (for_each_dist_pair with
 // its filter taking the hits instead of skipping them) and workspace layout.

@@ -41,8 +41,8 @@
 #if GK_IN(12) || GK_IN(14)
 #include "dist_simplex.h"       // the distance GJK's simplex arithmetic (host and device); part 14: the record helpers' constants
 #endif
-#if GK_IN(13)
-#include "cast_advance.h"       // the linear cast: conservative advancement over the distance GJK
+#if GK_IN(13) || GK_IN(15)
+#include "cast_advance.h"       // the linear and the rigid-motion cast: conservative advancement over the distance GJK
 #endif
 #if GK_IN(14)
 #include "manifold_clip.h"      // the contact manifold's plane geometry (host and device)
@@ -3114,7 +3114,7 @@ __global__ __launch_bounds__(64) void ws_reset_kernel(uint32_t* ws, int n32, uin
 }
 #endif  // GK_IN(0)
 
-#if GK_IN(12) || GK_IN(13) || GK_IN(14)
+#if GK_IN(12) || GK_IN(13) || GK_IN(14) || GK_IN(15)
 // ---------------------------------------------------------------- separation distance
 // gjkepa_distance_f64: 13 doubles (distance, point_a, point_b, normal, lambda), code[3], the four
 // int8 fields, iters, pad (the cast record: steps).  Its 16 8-byte words are stored from registers, word j by group lane j % G.
@@ -3178,8 +3178,8 @@ DEV bool manifold_hit(const unsigned char* records, int64_t p, int stride, int h
 // a hit of this tier's bracket), and only the pairs left go to the groups.  After a batch most
 // candidate pairs are hits (C2: 73%): handed to the groups they would leave three groups in four of
 // every round idle (measured, 2^20 C2 pairs: 1.99 ms with every pair handed out, 1.40 ms with this
-// filter; 2^22 C4 pairs 16.1 -> 10.5 ms).  ARGS: gjkepa_dist_args, or the cast's gjkepa_cast_args (the
-// same fields and its own skip flag).  HITS (the contact manifold, gjkepa_manifold_args): the filter
+// filter; 2^22 C4 pairs 16.1 -> 10.5 ms).  ARGS: gjkepa_dist_args, or the casts' gjkepa_cast_args /
+// gjkepa_cast_rigid_args (the same fields and their own skip flag).  HITS (the contact manifold, gjkepa_manifold_args): the filter
 // is turned round, the groups get the usable hits and the lane answers every other pair with NO_HIT.
 template <int G, int CAP, int TIER, bool HITS = false, typename ARGS, typename F>
 DEV void for_each_dist_pair(const Grp<G>& grp, const ARGS& a, F&& f) {
@@ -3286,7 +3286,7 @@ __global__ __launch_bounds__(64, MINW) void dist_kernel(const gjkepa_dist_args a
     for_each_dist_pair<G, G * K, TIER>(grp, a, body);
 }
 #endif  // GK_IN(12)
-#endif  // GK_IN(12) || GK_IN(13) || GK_IN(14)
+#endif  // GK_IN(12) || GK_IN(13) || GK_IN(14) || GK_IN(15)
 
 #if GK_IN(13)
 // ---------------------------------------------------------------- linear cast
@@ -3338,6 +3338,144 @@ __global__ __launch_bounds__(64, MINW) void cast_kernel(const gjkepa_cast_args a
     for_each_dist_pair<G, G * K, TIER>(grp, a, body);
 }
 #endif  // GK_IN(13)
+
+#if GK_IN(15)
+// ---------------------------------------------------------------- rigid-motion cast
+// Cast kernel of tier TIER for two bodies in rigid motion (include/gjkepa.h): the linear cast's shapes,
+// schedule and record packing, one group per pair.  cast_advance_rigid (cast_advance.h) runs the distance
+// GJK once per advancement step on the hulls posed by rigid_pose.h, group-uniform.  The hull image stays
+// unposed: a support is the unposed vertices' along the direction turned into each body's frame, so the two
+// hulls are scanned along two directions, and only the few simplex points are posed.  The two motions, the
+// step's pose state and the two radii are group-uniform values that every step needs but no inner loop
+// holds for long: they live in the group's LDS image beside the hulls and are read where they are used
+// (every lane of the group writes and reads the same values at the same addresses).
+template <typename TH, int G, int K> struct RigidLds {
+    Lds<double, TH, G, K, 0, 0> hull;
+    gkd::Motion mot[2];             // hull A's and hull B's motion: 2 x GJKEPA_MOTION_DOUBLES doubles
+    gkd::PoseState st[2];           // their pose at the step's time
+    double rho[2];                  // their farthest vertex from the pivot
+};
+static_assert(sizeof(gkd::Motion) == GJKEPA_MOTION_DOUBLES * sizeof(double), "a motion block is 9 packed doubles");
+
+// support_dots with a direction of its own per hull (da for hull A, db for hull B), indices only: the
+// same first-maximum rule, padding argument and reductions.
+CTX_T DEV void support_dots2(const CTX& c, V3<T> da, V3<T> db, int& ia, int& ib) {
+    T ta[K], tb[K];
+    T va = -Tol<T>::BIG, vb = -Tol<T>::BIG;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const V3<T> a = c.AV(k), b = c.BV(k);
+        ta[k] = da.x * a.x + da.y * a.y + da.z * a.z;
+        tb[k] = -(db.x * b.x + db.y * b.y + db.z * b.z);
+        va = red_max(ta[k], va);
+        vb = red_max(tb[k], vb);
+    }
+    va = gmax<G>(va);
+    vb = gmax<G>(vb);
+    const int sh = c.g.lane & ~(G - 1);
+    int xa = -1, xb = -1;
+#pragma unroll
+    for (int k = K - 1; k >= 0; --k) {
+        const uint64_t ma = (__ballot(ta[k] == va) >> sh) & (G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull));
+        const uint64_t mb = (__ballot(tb[k] == vb) >> sh) & (G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull));
+        if (ma) xa = k * G + (int)__builtin_ctzll(ma);
+        if (mb) xb = k * G + (int)__builtin_ctzll(mb);
+    }
+    ia = c.g.uni(xa < 0 ? 0 : xa);
+    ib = c.g.uni(xb < 0 ? 0 : xb);
+}
+// support_idx with two directions: the fp32-screened scan takes hull and direction separately already
+CTX_T DEV void support_idx2(const CTX& c, V3<T> da, V3<T> db, int& ia, int& ib) {
+    if constexpr (ScreenOn<K>::value && sizeof(T) == 8 && sizeof(TH) == 4) {
+        screened_idx(c, da, 0, c.vmax_a, ia);
+        if constexpr (GJKEPA_SCREEN_FENCE_MIN_G > 0 && G >= GJKEPA_SCREEN_FENCE_MIN_G) gk_lds_fence();
+        screened_idx(c, db, 1, c.vmax_b, ib);
+        return;
+    }
+    support_dots2(c, da, db, ia, ib);
+}
+// rho of hull h about the pivot p: one lane-parallel scan over the image (the slots past the count hold
+// vertex 0 again), the group's largest |x - p|^2, then one square root
+CTX_T DEV double pivot_radius(const CTX& c, int h, gkd::D3 p) {
+    double m = 0.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const V3<T> x = h ? c.B(k * G + c.g.gl) : c.A(k * G + c.g.gl);
+        const gkd::D3 q = gkd::sub(gkd::mk(x.x, x.y, x.z), p);
+        const double qq = gkd::dot(q, q);
+        m = qq > m ? qq : m;
+    }
+    return tsqrt(gmax<G>(m));
+}
+
+static_assert(gkd::kCastFlagImpact == GJKEPA_CAST_IMPACT && gkd::kCastFlagStart == GJKEPA_CAST_START &&
+              gkd::kCastStatusMaxIter == GJKEPA_STATUS_CAST_MAXITER && gkd::kMotionDoubles == GJKEPA_MOTION_DOUBLES,
+              "cast_advance.h and rigid_pose.h against gjkepa.h");
+template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
+__global__ __launch_bounds__(64, MINW) void cast_rigid_kernel(const gjkepa_cast_rigid_args a) {
+    using T = double;
+    using L_t = RigidLds<TIn, G, K>;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const Grp<G> grp;
+    L_t& L = *reinterpret_cast<L_t*>(smem + lds_stride<L_t, G>() * (grp.lane / G));
+    const int gl = grp.gl;
+    const TIn* verts = (const TIn*)a.verts;
+    auto body = [&](int64_t pair, const PairMeta& pm) {      // a pair of this tier with valid counts, not skipped
+        Ctx<T, TIn, G, K, 0, 0, LH> c{L.hull, grp};
+        double o13[13];
+#pragma unroll
+        for (int i = 0; i < 13; ++i) o13[i] = 0.0;
+        uint32_t code[3] = {gkd::kDistNoCode, gkd::kDistNoCode, gkd::kDistNoCode};
+        c.na = grp.uni(pm.na);
+        c.nb = grp.uni(pm.nb);
+        // the 18 motion doubles, one per group lane and round, into the image
+        const double* ma = a.body_motion + (int64_t)GJKEPA_MOTION_DOUBLES * a.pairs[2 * pair];
+        const double* mb = a.body_motion + (int64_t)GJKEPA_MOTION_DOUBLES * a.pairs[2 * pair + 1];
+        double* mot = reinterpret_cast<double*>(&L.mot[0]);
+        bool bad_motion = false;
+        for (int j = gl; j < 2 * GJKEPA_MOTION_DOUBLES; j += G) {
+            const double x = j < GJKEPA_MOTION_DOUBLES ? ma[j] : mb[j - GJKEPA_MOTION_DOUBLES];
+            bad_motion = bad_motion || !isfinite(x);
+            mot[j] = x;
+        }
+        bad_motion = grp.any(bad_motion);
+        if (load_hulls(c, verts + pm.oa, verts + pm.ob) || bad_motion) {
+            store_dist<G>(a.out, pair, gl, o13, code, 0, GJKEPA_STATUS_BAD_INPUT, 0, 0u);
+            __builtin_amdgcn_wave_barrier();
+            return;
+        }
+        L.rho[0] = pivot_radius(c, 0, L.mot[0].c);
+        L.rho[1] = pivot_radius(c, 1, L.mot[1].c);
+        gk_lds_fence();
+        auto posed_a = [&](int i) { const V3<T> p = c.A(i); return gkd::pose_point(L.st[0], L.mot[0].c, gkd::mk(p.x, p.y, p.z)); };
+        auto posed_b = [&](int i) { const V3<T> p = c.B(i); return gkd::pose_point(L.st[1], L.mot[1].c, gkd::mk(p.x, p.y, p.z)); };
+        gkd::Simplex s;
+        const gkd::CastResult r = gkd::cast_advance_rigid(
+            s, L.mot[0], L.mot[1], L.rho[0], L.rho[1], a.tolerance,
+            [&](gkd::D3 dir, int& ia, int& ib) {
+                gk_lds_fence();
+                const gkd::D3 da = gkd::pose_dir(L.st[0], dir), db = gkd::pose_dir(L.st[1], dir);
+                support_idx2(c, vmk<T>(da.x, da.y, da.z), vmk<T>(db.x, db.y, db.z), ia, ib);
+            },
+            [&](int ia, int ib) {
+                gk_lds_fence();
+                return gkd::sub(posed_a(ia), posed_b(ib));
+            },
+            [&](double t) {
+                L.st[0] = gkd::pose_state(L.mot[0].v, L.mot[0].w, t);
+                L.st[1] = gkd::pose_state(L.mot[1].v, L.mot[1].w, t);
+                gk_lds_fence();
+            },
+            [](double x) { return tsqrt(x); });
+        int n, status, flags;
+        gkd::cast_record_rigid(r, s, posed_a, posed_b, [](double x) { return tsqrt(x); }, o13, code, n, status, flags);
+        __builtin_amdgcn_wave_barrier();
+        store_dist<G>(a.out, pair, gl, o13, code, n, status, flags, r.iters, (uint32_t)r.steps);
+        __builtin_amdgcn_wave_barrier();
+    };
+    for_each_dist_pair<G, G * K, TIER>(grp, a, body);
+}
+#endif  // GK_IN(15)
 
 #if GK_IN(14)
 // ---------------------------------------------------------------- contact manifold
@@ -3490,7 +3628,7 @@ __global__ __launch_bounds__(64, MINW) void manifold_kernel(const gjkepa_manifol
 // only its own kernels so the parts compile in parallel: 0 = chain reset, query service and the launch
 // dispatchers, 1 = one-wave query path (fp64 compute), 2 = GJK tiers, 3 = contact tiers, 4 + t = EPA
 // tier t, 10 = one-wave query path (fp32 compute), 11 = fp32 redo, 12 = separation distance tiers,
-// 13 = linear cast tiers, 14 = contact manifold tiers.
+// 13 = linear cast tiers, 14 = contact manifold tiers, 15 = rigid-motion cast tiers.
 // Without GK_PART (diagnostic variant builds) one object holds every part.  The non-template kernels
 // (chain reset, query service) are defined in part 0 only.
 // the one-wave query path in fp32 compute (part 10)
@@ -3696,7 +3834,7 @@ hipError_t gjkepa_launch_gjk(int tier, int vert_dtype, int precision, const gjke
 
 #endif
 
-#if GK_IN(12) || GK_IN(13) || GK_IN(14)
+#if GK_IN(12) || GK_IN(13) || GK_IN(14) || GK_IN(15)
 namespace {
 // The distance, cast and manifold tiers launch alike, on GJK tier t's group shape.  FAM names the kernel
 // family: FAM::kernel<TIn, G, K, MINW, LH, TIER>, its waves per SIMD FAM::minw[tier] and a group's LDS
@@ -3759,6 +3897,21 @@ struct ManifoldTiers {
 hipError_t gjkepa_launch_manifold(int tier, int vert_dtype, const gjkepa_manifold_args& a, hipStream_t s) {
     return vert_dtype == GJKEPA_DTYPE_F32 ? pair_tier_any<ManifoldTiers, float>(tier, a, s)
                                           : pair_tier_any<ManifoldTiers, double>(tier, a, s);
+}
+#endif
+
+#if GK_IN(15)
+namespace {
+struct CastRigidTiers {
+    static constexpr int minw[3] = {GJKEPA_R0_MINW, GJKEPA_R1_MINW, GJKEPA_R2_MINW};
+    template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
+    static constexpr auto kernel = gk::cast_rigid_kernel<TIn, G, K, MINW, LH, TIER>;
+    template <typename TIn, int G, int K> using Image = gk::RigidLds<TIn, G, K>;
+};
+}  // namespace
+hipError_t gjkepa_launch_cast_rigid(int tier, int vert_dtype, const gjkepa_cast_rigid_args& a, hipStream_t s) {
+    return vert_dtype == GJKEPA_DTYPE_F32 ? pair_tier_any<CastRigidTiers, float>(tier, a, s)
+                                          : pair_tier_any<CastRigidTiers, double>(tier, a, s);
 }
 #endif
 

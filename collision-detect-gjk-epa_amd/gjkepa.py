@@ -31,6 +31,7 @@ MANIFOLD_MAX_FEATURE = 32                    # feature vertices used per hull (g
 DTYPE_F32, DTYPE_F64 = 0, 1
 PREC_F32, PREC_F64 = 0, 1
 MAX_HULL_VERTS = 256
+MOTION_DOUBLES = 9                           # a body's motion over the step: v[3], w[3], c[3] (gjkepa_cast_rigid_batch)
 
 # exported symbols declared in include/gjkepa.h
 EXPORTS = (
@@ -46,6 +47,8 @@ EXPORTS = (
     "gjkepa_distance_record_bytes", "gjkepa_distance_workspace_bytes", "gjkepa_distance_batch_device",
     "gjkepa_distance_batch",
     "gjkepa_cast_record_bytes", "gjkepa_cast_workspace_bytes", "gjkepa_cast_batch_device", "gjkepa_cast_batch",
+    "gjkepa_cast_rigid_workspace_bytes", "gjkepa_cast_rigid_batch_device", "gjkepa_cast_rigid_batch",
+    "gjkepa_pose_pool_device", "gjkepa_pose_pool",
     "gjkepa_manifold_record_bytes", "gjkepa_manifold_workspace_bytes", "gjkepa_manifold_batch_device",
     "gjkepa_manifold_batch",
 )
@@ -120,7 +123,7 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib = ctypes.CDLL(p)
     c_i32, c_i64, c_dbl, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
     # the size queries: *_workspace_bytes(n_pairs) -> int64, *_record_bytes(void) -> int
-    for q in ("gjkepa", "gjkepa_distance", "gjkepa_cast", "gjkepa_manifold", "gjkepa_compact"):
+    for q in ("gjkepa", "gjkepa_distance", "gjkepa_cast", "gjkepa_cast_rigid", "gjkepa_manifold", "gjkepa_compact"):
         fn = getattr(lib, q + "_workspace_bytes")
         fn.argtypes, fn.restype = [c_i64], c_i64
     for q in ("gjkepa_distance", "gjkepa_cast", "gjkepa_manifold"):
@@ -202,6 +205,14 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.gjkepa_cast_batch.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_dbl, c_vp, c_i32, c_vp,
                                       c_i32]
     lib.gjkepa_cast_batch.restype = ctypes.c_int
+    lib.gjkepa_cast_rigid_batch_device.argtypes = lib.gjkepa_cast_batch_device.argtypes      # body_motion for motion
+    lib.gjkepa_cast_rigid_batch_device.restype = ctypes.c_int
+    lib.gjkepa_cast_rigid_batch.argtypes = lib.gjkepa_cast_batch.argtypes
+    lib.gjkepa_cast_rigid_batch.restype = ctypes.c_int
+    lib.gjkepa_pose_pool_device.argtypes = [c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]
+    lib.gjkepa_pose_pool_device.restype = ctypes.c_int
+    lib.gjkepa_pose_pool.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32]
+    lib.gjkepa_pose_pool.restype = ctypes.c_int
     lib.gjkepa_manifold_batch_device.argtypes = lib.gjkepa_distance_batch_device.argtypes    # margin for max_distance
     lib.gjkepa_manifold_batch_device.restype = ctypes.c_int
     lib.gjkepa_manifold_batch.argtypes = lib.gjkepa_distance_batch.argtypes
@@ -500,6 +511,84 @@ def cast_batch_device(vert_dtype: int, verts_ptr: int, hull_off_ptr: int, hull_c
                                          int(n_pairs), motion_ptr, float(tolerance), records_ptr or None,
                                          int(records_precision), out_ptr, ws_ptr, int(ws_bytes), stream or None)
     _check(rc, "gjkepa_cast_batch_device")
+
+
+# ---- rigid-motion cast and the pose that goes with it (include/gjkepa.h gjkepa_cast_rigid_*, gjkepa_pose_pool*) ----
+def cast_rigid_workspace_bytes(n_pairs: int) -> int:
+    b = int(load().gjkepa_cast_rigid_workspace_bytes(int(n_pairs)))
+    if b < 0:
+        raise GjkEpaError("gjkepa_cast_rigid_workspace_bytes: bad arguments")
+    return b
+
+
+def _motion_arg(pool: HullPool, body_motion) -> np.ndarray:
+    mot = np.ascontiguousarray(body_motion, np.float64).reshape(-1)
+    if mot.size != MOTION_DOUBLES * len(pool.hull_cnt):
+        raise GjkEpaError("body_motion: 9 float64 (v, w, c) per hull of the pool")
+    return mot
+
+
+def cast_rigid_batch(pool: HullPool, body_motion, tolerance: float, records: np.ndarray | None = None,
+                     device: int = 0) -> np.ndarray:
+    """Cast of every pair of the pool with both bodies in rigid motion (host buffers, blocking); returns
+    CAST64 records.  body_motion: (n_hulls, 9) float64 per hull of the pool: v, the pivot's displacement
+    over the step; w, the rotation vector (angular velocity times the step; |w| = 2 tan(theta / 2) for a
+    turn by theta); c, the pivot at t = 0.  tolerance, flags and records as for cast_batch; status
+    STATUS_CAST_MAXITER: undecided, toi = the last time certified free.  Move the bodies with pose_pool."""
+    out = np.zeros(pool.n_pairs, dtype=CAST64)
+    keep, pool_args = _pool_args(pool)
+    mot = _motion_arg(pool, body_motion)
+    records, rec_ptr, rec_prec = _records_arg(records, pool.n_pairs)
+    rc = load().gjkepa_cast_rigid_batch(pool.dtype_code, *pool_args, _ptr(mot), float(tolerance), rec_ptr, rec_prec,
+                                        _ptr(out), int(device))
+    _check(rc, "gjkepa_cast_rigid_batch")
+    return out
+
+
+def cast_rigid_batch_device(vert_dtype: int, verts_ptr: int, hull_off_ptr: int, hull_cnt_ptr: int, pairs_ptr: int,
+                            n_pairs: int, body_motion_ptr: int, tolerance: float, records_ptr: int,
+                            records_precision: int, out_ptr: int, ws_ptr: int, ws_bytes: int, stream: int = 0) -> None:
+    """Device-resident rigid-motion cast (raw device pointers; body_motion: 9 doubles per hull),
+    asynchronous on `stream`; records_ptr 0 / None: no contact records."""
+    rc = load().gjkepa_cast_rigid_batch_device(int(vert_dtype), verts_ptr, hull_off_ptr, hull_cnt_ptr, pairs_ptr,
+                                               int(n_pairs), body_motion_ptr, float(tolerance), records_ptr or None,
+                                               int(records_precision), out_ptr, ws_ptr, int(ws_bytes), stream or None)
+    _check(rc, "gjkepa_cast_rigid_batch_device")
+
+
+def pose_pool(pool: HullPool, body_motion, time=None, out_dtype=None, device: int = 0, return_status: bool = False):
+    """The pool with every hull h moved along its body's path to time[h] (None: t = 1): the pose the
+    rigid-motion cast certifies (host buffers, blocking).  out_dtype: float32 / float64 (default: the
+    pool's); float64 is the cast's arithmetic exactly.  Hulls with a bad count or a non-finite motion, time
+    or vertex keep their vertices; return_status: also return the int8 status per hull."""
+    verts = np.ascontiguousarray(pool.verts)
+    off = np.ascontiguousarray(pool.hull_off, np.int64)
+    cnt = np.ascontiguousarray(pool.hull_cnt, np.int32)
+    mot = _motion_arg(pool, body_motion)
+    tm = None if time is None else np.ascontiguousarray(time, np.float64).reshape(-1)
+    if tm is not None and tm.size != cnt.size:
+        raise GjkEpaError("time: one float64 per hull of the pool")
+    out = verts.astype(np.dtype(out_dtype or verts.dtype))     # a copy: untouched scalars keep the input's values
+    if out.dtype not in (np.float32, np.float64):
+        raise GjkEpaError("out_dtype: float32 or float64")
+    status = np.zeros(cnt.size, np.int8)
+    rc = load().gjkepa_pose_pool(pool.dtype_code, _ptr(verts), verts.size, _ptr(off), _ptr(cnt), cnt.size, _ptr(mot),
+                                 None if tm is None else _ptr(tm), DTYPE_F32 if out.dtype == np.float32 else DTYPE_F64,
+                                 _ptr(out), _ptr(status), int(device))
+    _check(rc, "gjkepa_pose_pool")
+    posed = HullPool(out, pool.hull_off, pool.hull_cnt, pool.pairs)
+    return (posed, status) if return_status else posed
+
+
+def pose_pool_device(in_dtype: int, verts_in_ptr: int, hull_off_ptr: int, hull_cnt_ptr: int, n_hulls: int,
+                     body_motion_ptr: int, time_ptr: int, out_dtype: int, verts_out_ptr: int, status_ptr: int = 0,
+                     stream: int = 0) -> None:
+    """Device-resident pose (raw device pointers), asynchronous on `stream`; time_ptr 0 / None: t = 1;
+    status_ptr 0 / None: no status; verts_out_ptr may be verts_in_ptr when the dtypes are equal."""
+    rc = load().gjkepa_pose_pool_device(int(in_dtype), verts_in_ptr, hull_off_ptr, hull_cnt_ptr, int(n_hulls),
+                                        body_motion_ptr, time_ptr or None, int(out_dtype), verts_out_ptr,
+                                        status_ptr or None, stream or None)
+    _check(rc, "gjkepa_pose_pool_device")
 
 
 # ---- contact manifold of colliding pairs (include/gjkepa.h gjkepa_manifold_*) --------------------------

@@ -388,7 +388,7 @@ int gjkepa_distance_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_
  * (B's displacement minus A's over the step; fp64, always 3 doubles per pair), B(t) = B + t d for t in
  * [0, 1]: do the hulls come within `tolerance` (an absolute distance tau, finite and > 0) of each
  * other, when first, and where?  A ray cast is the case of a one-vertex hull A.  Linear motion only:
- * angular motion is out of scope.
+ * angular motion is out of scope (of this entry: gjkepa_cast_rigid_batch below casts spinning bodies).
  * Conservative advancement in fp64 over the distance GJK above, on the same group shapes:
  *   t = 0; at each step the distance GJK runs on A and B + t d (Minkowski points a - b - t d), the
  *   simplex carried from the step before by its codes.  OVERLAP at t = 0: START.  A separation
@@ -461,6 +461,81 @@ int gjkepa_cast_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scal
                       const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
                       const int32_t* pairs, int64_t n_pairs, const double* motion, double tolerance,
                       const void* records, int32_t records_precision, void* out, int32_t device);
+
+/* ---- rigid-motion cast (time of impact under rotation) and the pose that goes with it ----------
+ * The linear cast above with both bodies in full rigid motion.  A body is a hull of the pool; its motion
+ * over the step is GJKEPA_MOTION_DOUBLES = 9 doubles at body_motion[9 h] (per hull, not per pair: pair
+ * (a, b) reads blocks a and b):
+ *   v[3]  displacement of the pivot over the step
+ *   w[3]  rotation vector: angular velocity times the step
+ *   c[3]  pivot in world coordinates at t = 0, normally the centre of mass
+ * Path.  For t in [0, 1] a vertex p of the body is at
+ *   h = (0.5 t) w;  q = p - c;  u = h x q;  g = u + h x u;  f = 2 / (1 + h.h)
+ *   p(t) = (p + t v) + f g
+ * in fp64 without FMA contraction, exactly as written (csrc/rigid_pose.h): the rotation of the
+ * unnormalised quaternion (1, h) about the pivot, the pose the first-order update q <- normalize(q +
+ * 1/2 t w q) produces.  One division, no sin or cos: host and device give the same bytes.  t = 0 gives p
+ * exactly; w = 0 gives p + t v exactly.  The axis is w / |w| throughout and the angle is theta(t) =
+ * 2 atan(t |w| / 2), below half a turn, with theta'(t) = |w| / (1 + t^2 |w|^2 / 4) <= |w|.  A caller who
+ * integrates with the exponential map by an angle theta passes |w| = 2 tan(theta / 2).
+ * Cast.  Conservative advancement in fp64 over the distance GJK on A(t) and B(t).  At a visited time the
+ * GJK runs on the Minkowski points a_ia(t) - b_ib(t), the simplex carried by its codes (a valid start,
+ * reduced from scratch).  The support of a posed hull along dir is taken on the unposed vertices along
+ * R(t)^T dir (the same formula with -h applied to dir).  With n the unit normal from B to A, lb the
+ * support gap along n and rho_X = max_i |x_i - c_X|, the closing rate is
+ *   s = n.(v_B - v_A) + |n x w_A| rho_A + |n x w_B| rho_B
+ * (the velocity of a vertex along the fixed n is theta' r(t).(n x k) <= |w| |n x k| |r|: a spin about
+ * the contact normal costs nothing).  OVERLAP at t = 0: START.  Separation <= tau: START at step 0,
+ * IMPACT with toi = t later.  s <= 0: MISS (the plane n keeps separating).  Otherwise dt = (lb - tau / 2)
+ * / s; t + dt >= 1 is a MISS, n still separating the posed hulls at t = 1 by at least tau / 2; else
+ * t += dt.  GJKEPA_STATUS_CAST_MAXITER with toi = the last time certified free after 64 advancement
+ * steps, a step without progress, an OVERLAP after the first step or an inner run at its 64-iteration
+ * cap.  A pair whose closest approach lies between tau / 2 and tau may be reported either way.
+ * Record: gjkepa_cast_f64.  point_a / point_b are the witness points at toi in world coordinates, both
+ * posed; normal points from B to A (IMPACT, separated START) or is the normal of the plane separating at
+ * t = 1 (MISS); lambda, code, n_simplex as before (codes hold unposed vertex indices); steps <= 64.
+ * records and SKIPPED as for the linear cast.  GJKEPA_STATUS_BAD_INPUT for a pair with a hull count
+ * outside 1 .. GJKEPA_MAX_HULL_VERTS, a non-finite vertex or a non-finite value among its 18 motion
+ * doubles (bad counts first, then SKIPPED, then the values).
+ * Limit.  The bound sees a body's spin through rho, its farthest vertex from the pivot: a large body
+ * turning about a distant pivot converges slowly and may end as CAST_MAXITER, toi still certified free.
+ * Pivots belong at each body's own centre.
+ * After the cast, move the bodies with gjkepa_pose_pool: a different rotation formula voids the
+ * certificate. */
+#define GJKEPA_MOTION_DOUBLES 9
+/* Bytes of device workspace (as gjkepa_cast_workspace_bytes); negative for n_pairs < 0. */
+int64_t gjkepa_cast_rigid_workspace_bytes(int64_t n_pairs);
+/* Device buffers, asynchronous on `stream`: the contract of gjkepa_cast_batch_device (three tier launches
+ * after the counter reset, nothing recorded for gjkepa_launch_timing, deterministic, a captured graph is
+ * a linear chain; the same error rules).  body_motion: device, 9 doubles per hull of the pool. */
+int gjkepa_cast_rigid_batch_device(int32_t vert_dtype, const void* verts, const int64_t* hull_off,
+                                   const int32_t* hull_cnt, const int32_t* pairs, int64_t n_pairs,
+                                   const double* body_motion, double tolerance,
+                                   const void* records, int32_t records_precision,
+                                   void* out, void* workspace, int64_t workspace_bytes, void* stream);
+/* Host buffers, blocking; the pool arguments and checks of gjkepa_cast_batch.  body_motion: 9 n_hulls
+ * doubles. */
+int gjkepa_cast_rigid_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
+                            const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                            const int32_t* pairs, int64_t n_pairs, const double* body_motion, double tolerance,
+                            const void* records, int32_t records_precision, void* out, int32_t device);
+/* Pose a hull pool along the same path: verts_out = every vertex of every hull h at time[h] (time ==
+ * NULL: t = 1), at the input pool's offsets.  out_dtype GJKEPA_DTYPE_F64 is exactly the cast's arithmetic,
+ * GJKEPA_DTYPE_F32 that rounded once.  verts_out == verts_in is allowed when the dtypes are equal.
+ * status: NULL or one int8 per hull, GJKEPA_STATUS_OK or _BAD_INPUT (a count outside 1 ..
+ * GJKEPA_MAX_HULL_VERTS, or a non-finite motion, time or vertex); nothing is written for a BAD_INPUT hull.
+ * Asynchronous on `stream`, one launch, no allocation.  n_hulls == 0 returns 0.  GJKEPA_E_ARG for a bad
+ * dtype, a null pointer, or in place with different dtypes. */
+int gjkepa_pose_pool_device(int32_t in_dtype, const void* verts_in, const int64_t* hull_off,
+                            const int32_t* hull_cnt, int64_t n_hulls, const double* body_motion,
+                            const double* time, int32_t out_dtype, void* verts_out, int8_t* status, void* stream);
+/* Host buffers, blocking; the pool checks of gjkepa_cast_batch without a pair list.  verts_out holds
+ * n_vert_scalars scalars of out_dtype; the scalars of no hull, and of BAD_INPUT hulls, keep what the caller
+ * put there. */
+int gjkepa_pose_pool(int32_t in_dtype, const void* verts_in, int64_t n_vert_scalars,
+                     const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                     const double* body_motion, const double* time, int32_t out_dtype, void* verts_out,
+                     int8_t* status, int32_t device);
 
 /* ---- contact manifold (up to 4 points) of colliding pairs --------------------------------------
  * The fourth question about a pair, for the pairs a batch calls a collision: a contact patch instead of
