@@ -31,6 +31,7 @@
 #include "gjkepa_kernel.h"
 #include "hull_kernel.h"
 #include "broadphase_kernel.h"
+#include "sweep_kernel.h"
 #include "contacts_kernel.h"
 #include "pose_kernel.h"
 #include "capi_internal.h"
@@ -1778,6 +1779,89 @@ int gjkepa_broadphase(int32_t vert_dtype, const void* verts, int64_t n_vert_scal
     rc = gjkepa_broadphase_device(vert_dtype, d->verts.p, d->off.as<const int64_t>(), d->cnt.as<const int32_t>(), n_hulls,
                                   d->b_pairs.as<int32_t>(), max_pairs, d->b_count.as<int64_t>(), d->b_ws.p,
                                   (int64_t)d->b_ws.cap, d->stream);
+    if (rc) return rc;
+    st.down(n_pairs, d->b_count, 8);
+    st.sync();
+    if ((rc = st.failed())) return rc;
+    const int64_t m = *n_pairs < max_pairs ? *n_pairs : max_pairs;
+    if (m > 0) {
+        st.down(pairs, d->b_pairs, (size_t)m * 8);
+        st.sync();
+    }
+    return st.failed();
+}
+
+// ---- swept broad phase: the pair list of the casts (include/gjkepa.h) ----------
+}  // extern "C"
+
+namespace {
+int sweep_args_ok(int32_t vert_dtype, int64_t n_hulls, int64_t max_pairs, double tolerance, double long_radius) {
+    if (n_hulls < 0 || max_pairs < 0 || n_hulls > INT32_MAX - 1 || max_pairs > INT32_MAX ||
+        (vert_dtype != GJKEPA_DTYPE_F32 && vert_dtype != GJKEPA_DTYPE_F64))
+        return fail(GJKEPA_E_ARG, "bad n_hulls/max_pairs/dtype");
+    if (!(tolerance > 0.0 && tolerance <= 1.7976931348623157e308))
+        return fail(GJKEPA_E_ARG, "tolerance is NaN, infinite, zero or negative");
+    if (!(long_radius >= 0.0)) return fail(GJKEPA_E_ARG, "long_radius is NaN or negative");
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t gjkepa_broadphase_swept_workspace_bytes(int64_t n_hulls, int64_t max_pairs) {
+    if (n_hulls < 0 || max_pairs < 0 || n_hulls > INT32_MAX - 1 || max_pairs > INT32_MAX) return GJKEPA_E_ARG;
+    const int64_t b = gjkepa_sweep_ws_bytes(n_hulls, max_pairs);
+    return b < 0 ? fail(GJKEPA_E_NODEVICE, "workspace query needs a HIP device") : b;
+}
+
+int gjkepa_broadphase_swept_device(int32_t vert_dtype, const void* verts, const int64_t* hull_off, const int32_t* hull_cnt,
+                                   int64_t n_hulls, const double* body_motion, double tolerance, double long_radius,
+                                   int32_t* pairs, int64_t max_pairs, int64_t* n_pairs, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+    int rc = sweep_args_ok(vert_dtype, n_hulls, max_pairs, tolerance, long_radius);
+    if (rc) return rc;
+    if (!n_pairs) return fail(GJKEPA_E_ARG, "null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e;
+    if (n_hulls == 0) {
+        e = hipMemsetAsync(n_pairs, 0, 8, s);
+        return e == hipSuccess ? 0 : hip_fail(e, "hipMemsetAsync");
+    }
+    if (!verts || !hull_off || !hull_cnt || !body_motion || !workspace || (max_pairs > 0 && !pairs))
+        return fail(GJKEPA_E_ARG, "null pointer");
+    bool small = false;
+    e = gjkepa_enqueue_sweep(vert_dtype, verts, hull_off, hull_cnt, n_hulls, body_motion, tolerance, long_radius, pairs,
+                             max_pairs, n_pairs, workspace, workspace_bytes, s, &small);
+    if (e != hipSuccess) return hip_fail(e, "swept broad phase launch");
+    return small ? fail(GJKEPA_E_WORKSPACE, "workspace too small") : 0;
+}
+
+int gjkepa_broadphase_swept(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars, const int64_t* hull_off,
+                            const int32_t* hull_cnt, int64_t n_hulls, const double* body_motion, double tolerance,
+                            double long_radius, int32_t* pairs, int64_t max_pairs, int64_t* n_pairs, int32_t device) {
+    if (n_vert_scalars < 0) return fail(GJKEPA_E_ARG, "bad sizes");
+    int rc = sweep_args_ok(vert_dtype, n_hulls, max_pairs, tolerance, long_radius);
+    if (rc) return rc;
+    if (!n_pairs || (max_pairs > 0 && !pairs)) return fail(GJKEPA_E_ARG, "null pointer");
+    *n_pairs = 0;
+    if (n_hulls == 0) return 0;
+    if (!verts || !hull_off || !hull_cnt || !body_motion) return fail(GJKEPA_E_ARG, "null pointer");
+    if ((rc = check_pool(nullptr, 0, hull_off, hull_cnt, n_hulls, n_vert_scalars, GJKEPA_MAX_HULL_VERTS))) return rc;
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
+    const int64_t wsb = gjkepa_sweep_ws_bytes(n_hulls, max_pairs);
+    if (wsb < 0) return fail(GJKEPA_E_HIP, "swept broad phase workspace query failed");
+    st.up_pool(vert_dtype, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls);
+    st.up(d->d_motion, body_motion, (size_t)n_hulls * GJKEPA_MOTION_DOUBLES * sizeof(double));
+    st.room(d->b_pairs, (size_t)max_pairs * 8 + 8);
+    st.room(d->b_count, 8);
+    st.room(d->b_ws, (size_t)wsb);
+    if ((rc = st.failed())) return rc;
+    rc = gjkepa_broadphase_swept_device(vert_dtype, d->verts.p, d->off.as<const int64_t>(), d->cnt.as<const int32_t>(),
+                                        n_hulls, d->d_motion.as<const double>(), tolerance, long_radius,
+                                        d->b_pairs.as<int32_t>(), max_pairs, d->b_count.as<int64_t>(), d->b_ws.p,
+                                        (int64_t)d->b_ws.cap, d->stream);
     if (rc) return rc;
     st.down(n_pairs, d->b_count, 8);
     st.sync();

@@ -51,6 +51,7 @@ EXPORTS = (
     "gjkepa_pose_pool_device", "gjkepa_pose_pool",
     "gjkepa_manifold_record_bytes", "gjkepa_manifold_workspace_bytes", "gjkepa_manifold_batch_device",
     "gjkepa_manifold_batch",
+    "gjkepa_broadphase_swept_workspace_bytes", "gjkepa_broadphase_swept_device", "gjkepa_broadphase_swept",
 )
 COMM_ID_BYTES = 128
 # workspace header word counting the park slots a gjkepa_batch_device call took (diagnostics; csrc/
@@ -157,6 +158,13 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.gjkepa_broadphase.restype = ctypes.c_int
     lib.gjkepa_broadphase_device.argtypes = [c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]
     lib.gjkepa_broadphase_device.restype = ctypes.c_int
+    lib.gjkepa_broadphase_swept_workspace_bytes.argtypes = [c_i64, c_i64]
+    lib.gjkepa_broadphase_swept_workspace_bytes.restype = c_i64
+    lib.gjkepa_broadphase_swept.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_dbl, c_dbl, c_vp, c_i64, c_vp, c_i32]
+    lib.gjkepa_broadphase_swept.restype = ctypes.c_int
+    lib.gjkepa_broadphase_swept_device.argtypes = [c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_dbl, c_dbl, c_vp, c_i64, c_vp, c_vp,
+                                                   c_i64, c_vp]
+    lib.gjkepa_broadphase_swept_device.restype = ctypes.c_int
     lib.gjkepa_synth_scene.argtypes = [ctypes.c_uint64, c_i64, c_i64, c_i32, c_i32, c_dbl, c_i32, c_vp, c_vp, c_vp]
     lib.gjkepa_synth_scene.restype = c_i64
     lib.gjkepa_compact_hits_device.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]
@@ -849,6 +857,48 @@ def broadphase_device(vert_dtype: int, verts_ptr: int, hull_off_ptr: int, hull_c
     rc = load().gjkepa_broadphase_device(int(vert_dtype), verts_ptr, hull_off_ptr, hull_cnt_ptr, int(n_hulls),
                                          pairs_ptr, int(max_pairs), n_pairs_ptr, ws_ptr, int(ws_bytes), stream or None)
     _check(rc, "gjkepa_broadphase_device")
+
+
+# ---- swept broad phase: the pair list of the casts (include/gjkepa.h gjkepa_broadphase_swept) ---
+def broadphase_swept(pool: HullPool, body_motion, tolerance: float, long_radius: float = float("inf"),
+                     max_pairs: int | None = None, device: int = 0):
+    """Candidate pairs (a < b, ascending) whose swept bounding balls can come within `tolerance` during the
+    step, on the GPU: the pair list of cast_rigid_batch.  body_motion as for cast_rigid_batch; long_radius
+    is tuning only (bodies with rho + |v| / 2 above it are tested against every body instead of through the
+    grid) and never changes the list.  Returns (pairs int32 [n, 2], n_found); with max_pairs None the list
+    is grown until it fits."""
+    lib = load()
+    verts = np.ascontiguousarray(pool.verts)
+    off = np.ascontiguousarray(pool.hull_off, np.int64)
+    cnt = np.ascontiguousarray(pool.hull_cnt, np.int32)
+    mot = _motion_arg(pool, body_motion)
+    cap = max_pairs if max_pairs is not None else max(16 * cnt.size, 1024)
+    while True:
+        out = np.zeros((max(cap, 1), 2), np.int32)
+        nf = np.zeros(1, np.int64)
+        rc = lib.gjkepa_broadphase_swept(pool.dtype_code, _ptr(verts), verts.size, _ptr(off), _ptr(cnt), cnt.size,
+                                         _ptr(mot), float(tolerance), float(long_radius), _ptr(out), cap, _ptr(nf),
+                                         int(device))
+        _check(rc, "gjkepa_broadphase_swept")
+        n = int(nf[0])
+        if n <= cap or max_pairs is not None:
+            return out[:min(n, cap)], n
+        cap = n
+
+
+def broadphase_swept_workspace_bytes(n_hulls: int, max_pairs: int) -> int:
+    return int(load().gjkepa_broadphase_swept_workspace_bytes(n_hulls, max_pairs))
+
+
+def broadphase_swept_device(vert_dtype: int, verts_ptr: int, hull_off_ptr: int, hull_cnt_ptr: int, n_hulls: int,
+                            body_motion_ptr: int, tolerance: float, long_radius: float, pairs_ptr: int,
+                            max_pairs: int, n_pairs_ptr: int, ws_ptr: int, ws_bytes: int, stream: int = 0) -> None:
+    """Device-resident swept broad phase (raw device pointers; body_motion: 9 doubles per hull), asynchronous
+    on `stream`."""
+    rc = load().gjkepa_broadphase_swept_device(int(vert_dtype), verts_ptr, hull_off_ptr, hull_cnt_ptr, int(n_hulls),
+                                               body_motion_ptr, float(tolerance), float(long_radius), pairs_ptr,
+                                               int(max_pairs), n_pairs_ptr, ws_ptr, int(ws_bytes), stream or None)
+    _check(rc, "gjkepa_broadphase_swept_device")
 
 
 # ---- contact-list compaction (SURVEY.md §8 rows f3 / e5) ----------------------------------------

@@ -537,6 +537,60 @@ int gjkepa_pose_pool(int32_t in_dtype, const void* verts_in, int64_t n_vert_scal
                      const double* body_motion, const double* time, int32_t out_dtype, void* verts_out,
                      int8_t* status, int32_t device);
 
+/* ---- swept broad phase: the pair list of the casts ------------------------------------------------
+ * gjkepa_broadphase lists the pairs that are close at t = 0; a cast exists for the pair that is far apart
+ * now and meets during the step.  This entry lists, from the pool and the per-hull motion blocks of the
+ * rigid cast (v, w, c), exactly the pairs whose swept bounding balls can come within `tolerance` during
+ * t in [0, 1]: the pair list of gjkepa_cast_rigid_batch (and, with w = 0, of the linear cast).
+ * Definition (csrc/swept_sphere.h; fp64, no FMA contraction, dot(a, b) = a.x b.x + a.y b.y + a.z b.z, the
+ * operation order written here, so a restatement gives the same bits).  Hull h with motion block
+ * m = body_motion + 9 h is valid when its count is in 1 .. GJKEPA_MAX_HULL_VERTS, every vertex is finite
+ * and every double of m is finite; an invalid hull takes part in no pair.
+ *   rho_h = sqrt(max_i dot(q_i, q_i)), q_i = x_i - c, the vertices widened to double (the rigid cast's
+ *   pivot radius: an order-free maximum, then one square root).  Under the cast's path the pivot moves on
+ *   c + t v and every vertex stays within rho_h of it, so w does not enter.
+ * A pair (a < b) of valid hulls passes when
+ *   d = c_a - c_b;  e = v_a - v_b;  ee = dot(e, e);  de = dot(d, e)
+ *   s = 0            if ee == 0 or de >= 0
+ *       1            else if -de >= ee
+ *       (-de) / ee   otherwise
+ *   m = (d.x + s e.x, d.y + s e.y, d.z + s e.z);   dist = sqrt(dot(m, m))
+ *   reach = (rho_a + rho_b) + tolerance
+ *   lim = reach + 1e-9 * ((reach + max|d_k|) + max|e_k|)
+ *   pass iff dist <= lim
+ * dist is the closest approach of the two ball centres over the step.  The 1e-9 term is part of the
+ * definition: it makes the list a superset of the pairs the casts can report as IMPACT or START at this
+ * tolerance despite rounding in either place.  Both that and the independence from
+ * long_radius below hold while coordinates stay below about 1e5 times (reach + |d| + |e|), i.e. bodies of
+ * size 1 out to coordinates of 1e5: beyond that the cast's own posed vertices are coarser than the slack, and
+ * past about 2^28 grid cells from the origin the grid (not the long path) may miss a passing pair.
+ * Output: the contract of gjkepa_broadphase_device.  The passing pairs in ascending (a, b) order;
+ * *n_pairs = n_found (device int64 for the device entry); the list holds min(n_found, max_pairs) of them,
+ * distinct and ascending, a subset when cut; the final sort runs over max_pairs padded keys.
+ * long_radius (>= 0, +inf for none) is tuning only and never changes the list: the grid's cell edge follows
+ * the largest enclosing radius R = rho + 0.5 |v|, so one bullet would turn the grid into an all-pairs test.
+ * A valid body with R > long_radius leaves the grid and is tested against every valid body instead; choose a
+ * few typical body diameters.  0 tests all pairs.
+ * Limit.  The test sees a body through rho about its pivot: a pivot far from the body inflates the list, as
+ * it slows the cast.  Pivots belong at each body's own centre.
+ * Errors: GJKEPA_E_ARG for a bad dtype, a null pointer, a tolerance that is NaN, infinite or <= 0, a
+ * long_radius that is NaN or negative; GJKEPA_E_WORKSPACE for a short workspace.  n_hulls == 0 gives
+ * *n_pairs = 0 and returns 0. */
+int64_t gjkepa_broadphase_swept_workspace_bytes(int64_t n_hulls, int64_t max_pairs);
+/* Device buffers, asynchronous on `stream`: no allocation, no synchronisation, no result that depends on an
+ * atomic (graph-capturable; replay after rewriting body_motion in place).  n_pairs is a device int64. */
+int gjkepa_broadphase_swept_device(int32_t vert_dtype, const void* verts, const int64_t* hull_off,
+                                   const int32_t* hull_cnt, int64_t n_hulls, const double* body_motion,
+                                   double tolerance, double long_radius,
+                                   int32_t* pairs, int64_t max_pairs, int64_t* n_pairs,
+                                   void* workspace, int64_t workspace_bytes, void* stream);
+/* Host buffers, blocking: the pool arguments and checks of gjkepa_broadphase.  body_motion: 9 n_hulls
+ * doubles. */
+int gjkepa_broadphase_swept(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
+                            const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                            const double* body_motion, double tolerance, double long_radius,
+                            int32_t* pairs, int64_t max_pairs, int64_t* n_pairs, int32_t device);
+
 /* ---- contact manifold (up to 4 points) of colliding pairs --------------------------------------
  * The fourth question about a pair, for the pairs a batch calls a collision: a contact patch instead of
  * the reference's one collision_point, as a solver needs for two boxes resting face to face.  It is

@@ -18,12 +18,12 @@ rm -f $OUT/k[0-9]*.o
 if [ "${SINGLE:-0}" = 1 ]; then
   /opt/rocm/bin/hipcc $F -c $S/gjkepa_kernel.hip -o $OUT/k0.o & PIDS="$!"
 else
-  for p in 0 1 2 3 4 5 6 7 8 9 10 11 12 13 14; do
+  for p in 0 1 2 3 4 5 6 7 8 9 10 11 12 13 14 15; do
     /opt/rocm/bin/hipcc $F -DGK_PART=$p -c $S/gjkepa_kernel.hip -o $OUT/k$p.o & PIDS="$PIDS $!"
   done
 fi
 /opt/rocm/bin/hipcc $F -DGJKEPA_SRC_HASH="\"variant-$NAME\"" -c $S/gjkepa_capi.cpp -o $OUT/c.o
 for pid in $PIDS; do wait $pid; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fopenmp $OUT/k[0-9]*.o $OUT/c.o $D/build/hull_kernel.o \
-    $D/build/broadphase_kernel.o $D/build/contacts_kernel.o $D/build/gjkepa_multi.o $D/build/synth.o -o $OUT/libgjkepa_hip.so -ldl -pthread -L/opt/rocm/lib -lrocprofiler-sdk-roctx
+    $D/build/broadphase_kernel.o $D/build/sweep_kernel.o $D/build/contacts_kernel.o $D/build/pose_kernel.o $D/build/gjkepa_multi.o $D/build/synth.o -o $OUT/libgjkepa_hip.so -ldl -pthread -L/opt/rocm/lib -lrocprofiler-sdk-roctx
 echo built $OUT/libgjkepa_hip.so
