@@ -34,6 +34,7 @@
 #include "sweep_kernel.h"
 #include "contacts_kernel.h"
 #include "pose_kernel.h"
+#include "events_kernel.h"
 #include "capi_internal.h"
 
 namespace {
@@ -107,6 +108,7 @@ struct DeviceState {
     DevBuf d_rec, d_out, d_ws;                              // gjkepa_distance_batch / gjkepa_cast_batch staging
     DevBuf d_motion;                                        // gjkepa_cast_batch / gjkepa_cast_rigid_batch / gjkepa_pose_pool staging
     DevBuf d_time, d_status;                                // gjkepa_pose_pool staging
+    DevBuf m_cast, m_events, m_ws, m_n, m_time, m_rank, m_posed;   // gjkepa_collide_moving staging
     HostBuf q_host;
 };
 
@@ -1901,6 +1903,38 @@ int gjkepa_compact_hits_device(int32_t precision, const void* records, int64_t n
     return e == hipSuccess ? 0 : hip_fail(e, "compaction launch");
 }
 
+// ---- event list and per-body clamp of a moving step (include/gjkepa.h) -----------
+int gjkepa_event_record_bytes(void) { return (int)sizeof(gjkepa_event_f64); }
+
+int64_t gjkepa_events_workspace_bytes(int64_t n_pairs, int64_t n_hulls) {
+    if (n_pairs < 0 || n_hulls < 0 || n_pairs > INT32_MAX || n_hulls > INT32_MAX) return GJKEPA_E_ARG;
+    const int64_t b = gjkepa_events_ws_bytes(n_pairs);
+    return b < 0 ? fail(GJKEPA_E_NODEVICE, "workspace query needs a HIP device") : b;
+}
+
+int gjkepa_events_device(const int32_t* pairs, int64_t n_pairs, int64_t n_hulls, const void* cast_records,
+                         const void* records, int32_t records_precision, void* events, int64_t max_events,
+                         int64_t* n_events, int64_t* counts, double* body_time, int32_t* body_event, void* workspace,
+                         int64_t workspace_bytes, void* stream) {
+    static_assert(sizeof(gjkepa_event_f64) == 128, "gjkepa_event_f64 layout (gjkepa.py EVENT64)");
+    if (n_pairs < 0 || n_hulls < 0 || max_events < 0 || n_pairs > INT32_MAX || n_hulls > INT32_MAX)
+        return fail(GJKEPA_E_ARG, "bad n_pairs/n_hulls/max_events");
+    if (records && records_precision != GJKEPA_PREC_F32 && records_precision != GJKEPA_PREC_F64)
+        return fail(GJKEPA_E_ARG, "bad records_precision");
+    if ((body_time == nullptr) != (body_event == nullptr)) return fail(GJKEPA_E_ARG, "body_time and body_event: both or neither");
+    if (!n_events || !counts || (max_events > 0 && !events)) return fail(GJKEPA_E_ARG, "null pointer");
+    if (n_pairs > 0 && (!pairs || !cast_records || !workspace)) return fail(GJKEPA_E_ARG, "null pointer");
+    // the part of the workspace that needs no device to size, then the whole
+    if (n_pairs > 0 && workspace_bytes < gjkepa_events_ws_floor(n_pairs)) return fail(GJKEPA_E_WORKSPACE, "workspace too small");
+    bool small = false;
+    const hipError_t e = gjkepa_enqueue_events(pairs, n_pairs, n_hulls, cast_records, records, records_precision,
+                                               records ? gjkepa_record_bytes(records_precision) : 0, events, max_events,
+                                               n_events, counts, body_time, body_event, workspace, workspace_bytes,
+                                               (hipStream_t)stream, &small);
+    if (e != hipSuccess) return hip_fail(e, "event pass launch");
+    return small ? fail(GJKEPA_E_WORKSPACE, "workspace too small") : 0;
+}
+
 // ---- whole collision step: broad phase -> narrow phase -> hit list (host buffers) ---------------
 int gjkepa_collide(int32_t version, double tol_ff, int32_t vert_dtype, int32_t precision, const void* verts,
                    int64_t n_vert_scalars, const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
@@ -1984,6 +2018,110 @@ int gjkepa_collide(int32_t version, double tol_ff, int32_t vert_dtype, int32_t p
         }
     }
     return 0;
+}
+
+// ---- whole moving step: swept broad phase -> narrow phase -> rigid cast -> events (-> pose) -------
+int gjkepa_collide_moving(int32_t version, double tol_ff, int32_t vert_dtype, int32_t precision, const void* verts,
+                          int64_t n_vert_scalars, const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                          const double* body_motion, double tolerance, double long_radius, void* events,
+                          int64_t max_events, int64_t* n_events, int64_t* counts, int64_t* n_candidates,
+                          double* body_time, void* verts_out, int32_t device) {
+    const gjkepa_internal::Range range_("gjkepa_collide_moving (swept broad phase, chain, cast, events)");
+    if (max_events < 0 || n_vert_scalars < 0 || !valid_enums(vert_dtype, precision))
+        return fail(GJKEPA_E_ARG, "bad sizes/dtype/precision");
+    int rc = sweep_args_ok(vert_dtype, n_hulls, 0, tolerance, long_radius);
+    if (rc) return rc;
+    if (!n_events || (max_events > 0 && !events)) return fail(GJKEPA_E_ARG, "null pointer");
+    *n_events = 0;
+    if (n_candidates) *n_candidates = 0;
+    for (int i = 0; counts && i < 5; ++i) counts[i] = 0;
+    if (n_hulls == 0) return 0;
+    if (!verts || !hull_off || !hull_cnt || !body_motion) return fail(GJKEPA_E_ARG, "null pointer");
+    if ((rc = check_pool(nullptr, 0, hull_off, hull_cnt, n_hulls, n_vert_scalars, GJKEPA_MAX_HULL_VERTS))) return rc;
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
+    const size_t rec = (size_t)gjkepa_record_bytes(precision);
+    const size_t pool_bytes = (size_t)n_vert_scalars * (vert_dtype == GJKEPA_DTYPE_F32 ? 4 : 8);
+    hipStream_t s = d->stream;
+    st.up_pool(vert_dtype, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls);
+    st.up(d->d_motion, body_motion, (size_t)n_hulls * GJKEPA_MOTION_DOUBLES * sizeof(double));
+    st.room(d->b_count, 8);
+    if ((rc = st.failed())) return rc;
+    const auto* off = d->off.as<const int64_t>();
+    const auto* cnt = d->cnt.as<const int32_t>();
+    const auto* motion = d->d_motion.as<const double>();
+    // swept broad phase: a list of 8 candidates per hull first; one more pass at the exact size if it was cut
+    int64_t cap = n_hulls * 8 > 1024 ? n_hulls * 8 : 1024, ncand = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (cap > INT32_MAX) return fail(GJKEPA_E_ARG, "candidate list above 2^31-1 pairs");
+        const int64_t wsb = gjkepa_sweep_ws_bytes(n_hulls, cap);
+        if (wsb < 0) return fail(GJKEPA_E_HIP, "swept broad phase workspace query failed");
+        st.room(d->b_pairs, (size_t)cap * 8 + 8);
+        st.room(d->b_ws, (size_t)wsb);
+        if ((rc = st.failed())) return rc;
+        rc = gjkepa_broadphase_swept_device(vert_dtype, d->verts.p, off, cnt, n_hulls, motion, tolerance, long_radius,
+                                            d->b_pairs.as<int32_t>(), cap, d->b_count.as<int64_t>(), d->b_ws.p,
+                                            (int64_t)d->b_ws.cap, s);
+        if (rc) return rc;
+        st.down(&ncand, d->b_count, 8);
+        st.sync();
+        if ((rc = st.failed())) return rc;
+        if (ncand <= cap) break;
+        cap = ncand;
+    }
+    if (n_candidates) *n_candidates = ncand;
+    // narrow phase on the device-resident list, the rigid cast with its records, the events
+    bool large = false;
+    for (int64_t h = 0; h < n_hulls && !large; ++h) large = hull_cnt[h] > kParkMinHull;
+    const int64_t wsn = ws_bytes_for(ncand, large ? ncand : 0), wse = gjkepa_events_ws_bytes(ncand);
+    if (wse < 0) return fail(GJKEPA_E_HIP, "event workspace query failed");
+    const int64_t m_max = ncand < max_events ? ncand : max_events;     // the list cannot be longer than the candidates
+    st.room(d->out, (size_t)ncand * rec);
+    st.room(d->ws, (size_t)wsn);
+    st.room(d->m_cast, (size_t)ncand * sizeof(gjkepa_cast_f64));
+    st.room(d->d_ws, (size_t)GJKEPA_CAST_WS_BYTES);
+    st.room(d->m_events, (size_t)m_max * sizeof(gjkepa_event_f64) + 16);
+    st.room(d->m_ws, (size_t)wse);
+    st.room(d->m_n, 6 * 8);
+    st.room(d->m_time, (size_t)n_hulls * 8);
+    st.room(d->m_rank, (size_t)n_hulls * 4);
+    if (verts_out) st.room(d->m_posed, pool_bytes);
+    if ((rc = st.failed())) return rc;
+    const auto* cand = d->b_pairs.as<const int32_t>();
+    if ((rc = enqueue(version, tol_ff, vert_dtype, precision, d->verts.p, off, cnt, cand, ncand, d->out.p, d->ws.p,
+                      (int64_t)d->ws.cap, s, d->num_cus)))
+        return rc;
+    if (ncand > 0 && (rc = cast_rigid_enqueue(PairQuery{vert_dtype, d->verts.p, off, cnt, cand, ncand, d->out.p, precision,
+                                                        d->m_cast.p, d->d_ws.p, (int64_t)d->d_ws.cap, s, d->num_cus},
+                                              motion, tolerance)))
+        return rc;
+    int64_t* dn = d->m_n.as<int64_t>();
+    if ((rc = gjkepa_events_device(cand, ncand, n_hulls, d->m_cast.p, d->out.p, precision, d->m_events.p, m_max, dn, dn + 1,
+                                   d->m_time.as<double>(), d->m_rank.as<int32_t>(), d->m_ws.p, (int64_t)d->m_ws.cap, s)))
+        return rc;
+    if (verts_out) {
+        // the scalars the pose leaves alone (no hull's, a bad hull's) hold the input's values
+        st.note(hipMemcpyAsync(d->m_posed.p, d->verts.p, pool_bytes, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync D2D");
+        if ((rc = st.failed())) return rc;
+        const gjkepa_pose_args a{d->verts.p, off, cnt, n_hulls, motion, d->m_time.as<const double>(), d->m_posed.p, nullptr};
+        const hipError_t e = gjkepa_launch_pose(vert_dtype, vert_dtype, a, d->num_cus, s);
+        if (e != hipSuccess) return hip_fail(e, "pose launch");
+        st.down(verts_out, d->m_posed, pool_bytes);
+    }
+    int64_t host_n[6] = {0, 0, 0, 0, 0, 0};
+    st.down(host_n, d->m_n, sizeof host_n);
+    if (body_time) st.down(body_time, d->m_time, (size_t)n_hulls * 8);
+    st.sync();
+    if ((rc = st.failed())) return rc;
+    *n_events = host_n[0];
+    for (int i = 0; counts && i < 5; ++i) counts[i] = host_n[1 + i];
+    const int64_t m = host_n[0] < m_max ? host_n[0] : m_max;
+    if (m > 0) {
+        st.down(events, d->m_events, (size_t)m * sizeof(gjkepa_event_f64));
+        st.sync();
+    }
+    return st.failed();
 }
 
 }  // extern "C"

@@ -52,6 +52,7 @@ EXPORTS = (
     "gjkepa_manifold_record_bytes", "gjkepa_manifold_workspace_bytes", "gjkepa_manifold_batch_device",
     "gjkepa_manifold_batch",
     "gjkepa_broadphase_swept_workspace_bytes", "gjkepa_broadphase_swept_device", "gjkepa_broadphase_swept",
+    "gjkepa_event_record_bytes", "gjkepa_events_workspace_bytes", "gjkepa_events_device", "gjkepa_collide_moving",
 )
 COMM_ID_BYTES = 128
 # workspace header word counting the park slots a gjkepa_batch_device call took (diagnostics; csrc/
@@ -93,6 +94,16 @@ MANIFOLD64 = np.dtype([
     ("reserved", "i1"), ("area", "<f8"),
 ])
 assert MANIFOLD64.itemsize == 160
+# gjkepa_event_f64 (include/gjkepa.h): one per event from events / events_device / collide_moving
+EVENT_HIT, EVENT_START, EVENT_IMPACT, EVENT_UNDECIDED = 1, 2, 3, 4
+EVENT64 = np.dtype([
+    ("time", "<f8"), ("point_a", "<f8", (3,)), ("point_b", "<f8", (3,)), ("normal", "<f8", (3,)), ("depth", "<f8"),
+    ("a", "<i4"), ("b", "<i4"), ("pair", "<i4"), ("kind", "i1"), ("status", "i1"), ("reserved", "i1", (2,)),
+    ("pad", "<u4", (6,)),
+])
+assert EVENT64.itemsize == 128
+event_dtype = EVENT64
+EVENTS_TILE = 4096                           # records per block of the event pass's key pass (csrc/events_kernel.h)
 
 
 def record_dtype(precision: int) -> np.dtype:
@@ -225,6 +236,14 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.gjkepa_manifold_batch_device.restype = ctypes.c_int
     lib.gjkepa_manifold_batch.argtypes = lib.gjkepa_distance_batch.argtypes
     lib.gjkepa_manifold_batch.restype = ctypes.c_int
+    lib.gjkepa_event_record_bytes.argtypes, lib.gjkepa_event_record_bytes.restype = [], ctypes.c_int
+    lib.gjkepa_events_workspace_bytes.argtypes, lib.gjkepa_events_workspace_bytes.restype = [c_i64, c_i64], c_i64
+    lib.gjkepa_events_device.argtypes = [c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                         c_i64, c_vp]
+    lib.gjkepa_events_device.restype = ctypes.c_int
+    lib.gjkepa_collide_moving.argtypes = [c_i32, c_dbl, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_dbl, c_dbl,
+                                          c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32]
+    lib.gjkepa_collide_moving.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -899,6 +918,101 @@ def broadphase_swept_device(vert_dtype: int, verts_ptr: int, hull_off_ptr: int, 
                                                body_motion_ptr, float(tolerance), float(long_radius), pairs_ptr,
                                                int(max_pairs), n_pairs_ptr, ws_ptr, int(ws_bytes), stream or None)
     _check(rc, "gjkepa_broadphase_swept_device")
+
+
+# ---- event list and per-body clamp of a moving step (include/gjkepa.h gjkepa_events_device) ------
+def events_workspace_bytes(n_pairs: int, n_hulls: int) -> int:
+    b = int(load().gjkepa_events_workspace_bytes(int(n_pairs), int(n_hulls)))
+    if b < 0:
+        raise GjkEpaError(f"gjkepa_events_workspace_bytes failed ({b})")
+    return b
+
+
+def events_device(pairs_ptr: int, n_pairs: int, n_hulls: int, cast_records_ptr: int, records_ptr: int,
+                  records_precision: int, events_ptr: int, max_events: int, n_events_ptr: int, counts_ptr: int,
+                  body_time_ptr: int, body_event_ptr: int, ws_ptr: int, ws_bytes: int, stream: int = 0) -> None:
+    """Device-resident event pass (raw device pointers), asynchronous on `stream`: the events of a pair list's
+    cast records in (time, pair) order, *n_events and counts[5] (device int64), and per hull the first IMPACT
+    or UNDECIDED event's time and rank.  records_ptr 0 / None: no contact records; body_time_ptr and
+    body_event_ptr both 0 / None: no body outputs."""
+    rc = load().gjkepa_events_device(pairs_ptr or None, int(n_pairs), int(n_hulls), cast_records_ptr or None,
+                                     records_ptr or None, int(records_precision), events_ptr or None, int(max_events),
+                                     n_events_ptr, counts_ptr, body_time_ptr or None, body_event_ptr or None,
+                                     ws_ptr or None, int(ws_bytes), stream or None)
+    _check(rc, "gjkepa_events_device")
+
+
+def events(pairs, cast_records, n_hulls: int, records: np.ndarray | None = None, max_events: int | None = None,
+           bodies: bool = True, device: int = 0):
+    """The event pass over host arrays, staged through torch (for tests and tools; a pipeline keeps its records
+    on the device and calls events_device).  pairs: int32 (n, 2); cast_records: CAST64 (n,); records: None or
+    the list's REC64 / REC32 contact records; max_events None: room for every event.
+    Returns (events EVENT64 [min(n_events, max_events)], n_events, counts int64 [5], body_time float64
+    [n_hulls] or None, body_event int32 [n_hulls] or None)."""
+    import torch
+    prs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    n = prs.shape[0]
+    cast = np.ascontiguousarray(cast_records)
+    if cast.dtype != CAST64 or cast.shape != (n,):
+        raise GjkEpaError("cast_records: one CAST64 record per pair")
+    records, _, rec_prec = _records_arg(records, n)
+    cap = n if max_events is None else int(max_events)
+    dev = torch.device("cuda", int(device))
+
+    def to_dev(a):
+        return torch.from_numpy(a.view(np.uint8).reshape(-1)).to(dev)
+
+    with torch.cuda.device(dev):
+        d_prs, d_cast = to_dev(prs), to_dev(cast)
+        d_rec = None if records is None else to_dev(records)
+        d_ev = torch.zeros(max(cap, 1) * EVENT64.itemsize, dtype=torch.uint8, device=dev)
+        d_n = torch.zeros(6, dtype=torch.int64, device=dev)
+        d_time = torch.zeros(max(n_hulls, 1), dtype=torch.float64, device=dev) if bodies else None
+        d_rank = torch.zeros(max(n_hulls, 1), dtype=torch.int32, device=dev) if bodies else None
+        wsb = events_workspace_bytes(n, n_hulls)
+        ws = torch.zeros(max(wsb, 256), dtype=torch.uint8, device=dev)
+        events_device(d_prs.data_ptr() if n else 0, n, n_hulls, d_cast.data_ptr() if n else 0,
+                      0 if d_rec is None else d_rec.data_ptr(), rec_prec, d_ev.data_ptr(), cap, d_n.data_ptr(),
+                      d_n.data_ptr() + 8, d_time.data_ptr() if bodies else 0, d_rank.data_ptr() if bodies else 0,
+                      ws.data_ptr(), wsb, torch.cuda.current_stream(dev).cuda_stream)
+        torch.cuda.current_stream(dev).synchronize()
+    host_n = d_n.cpu().numpy()
+    m = min(int(host_n[0]), cap)
+    ev = d_ev.cpu().numpy()[:m * EVENT64.itemsize].view(EVENT64).copy()
+    if not bodies:
+        return ev, int(host_n[0]), host_n[1:6].copy(), None, None
+    return ev, int(host_n[0]), host_n[1:6].copy(), d_time.cpu().numpy()[:n_hulls], d_rank.cpu().numpy()[:n_hulls]
+
+
+def collide_moving(pool: HullPool, body_motion, tolerance: float, long_radius: float = float("inf"), version: int = 2,
+                   tol_ff: float = 1.0, precision: int = PREC_F64, max_events: int | None = None, pose: bool = False,
+                   device: int = 0):
+    """A whole moving step over a hull pool in one call (host buffers, blocking): swept broad phase, narrow
+    phase on its list, rigid cast with the batch's records, event pass, and with pose=True the pool posed at
+    body_time.  body_motion, tolerance and long_radius as for broadphase_swept.  With max_events None the list
+    is grown until it fits.  Returns a dict: events (EVENT64), n_events, counts (int64 [5]: HIT, START, IMPACT,
+    UNDECIDED, BAD), n_candidates, body_time (float64 [n_hulls]) and posed (a HullPool, or None)."""
+    lib = load()
+    verts = np.ascontiguousarray(pool.verts)
+    off = np.ascontiguousarray(pool.hull_off, np.int64)
+    cnt = np.ascontiguousarray(pool.hull_cnt, np.int32)
+    mot = _motion_arg(pool, body_motion)
+    cap = max_events if max_events is not None else max(4 * cnt.size, 1024)
+    while True:
+        ev = np.zeros(max(cap, 1), EVENT64)
+        ne, ncand, counts = np.zeros(1, np.int64), np.zeros(1, np.int64), np.zeros(5, np.int64)
+        btime = np.zeros(cnt.size)
+        posed = verts.copy() if pose else None
+        rc = lib.gjkepa_collide_moving(int(version), float(tol_ff), pool.dtype_code, int(precision), _ptr(verts), verts.size,
+                                       _ptr(off), _ptr(cnt), cnt.size, _ptr(mot), float(tolerance), float(long_radius),
+                                       _ptr(ev), cap, _ptr(ne), _ptr(counts), _ptr(ncand), _ptr(btime),
+                                       _ptr(posed) if pose else None, int(device))
+        _check(rc, "gjkepa_collide_moving")
+        n = int(ne[0])
+        if n <= cap or max_events is not None:
+            return {"events": ev[:min(n, cap)], "n_events": n, "counts": counts, "n_candidates": int(ncand[0]),
+                    "body_time": btime, "posed": HullPool(posed, pool.hull_off, pool.hull_cnt, pool.pairs) if pose else None}
+        cap = n
 
 
 # ---- contact-list compaction (SURVEY.md §8 rows f3 / e5) ----------------------------------------

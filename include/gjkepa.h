@@ -591,6 +591,103 @@ int gjkepa_broadphase_swept(int32_t vert_dtype, const void* verts, int64_t n_ver
                             const double* body_motion, double tolerance, double long_radius,
                             int32_t* pairs, int64_t max_pairs, int64_t* n_pairs, int32_t device);
 
+/* ---- event list and per-body clamp of a moving step -------------------------------------------------
+ * The casts leave one record per candidate pair, MISS or not, in pair order.  This pass turns the cast
+ * records of a pair list (and, for the pairs already in contact, the batch's contact records) into what
+ * happened during the step, in the order it happened: a dense list of events sorted by time, and for every
+ * body the earliest event that stops it, as the time gjkepa_pose_pool takes per hull.
+ * Definition (csrc/event_record.h is its text, for host and device).  The kind of a pair comes from its cast
+ * record alone (gjkepa_cast_f64 of the linear or the rigid cast); the first rule that applies wins:
+ *   1. status GJKEPA_STATUS_BAD_INPUT     no event, counted as BAD
+ *   2. flag GJKEPA_CAST_SKIPPED           GJKEPA_EVENT_HIT, time 0
+ *   3. status GJKEPA_STATUS_CAST_MAXITER  GJKEPA_EVENT_UNDECIDED, time = toi, the last time certified free
+ *   4. flag GJKEPA_CAST_START             GJKEPA_EVENT_START, time 0
+ *   5. flag GJKEPA_CAST_IMPACT            GJKEPA_EVENT_IMPACT, time = toi
+ *   6. otherwise (a MISS)                 no event
+ * time is toi when toi > 0, else +0.0 (a NaN toi gives 0), so the bits of time, read as uint64, order like
+ * the value.
+ *   time       0 for HIT / START; toi for IMPACT / UNDECIDED
+ *   point_a/b, normal   START, IMPACT, UNDECIDED: the cast record's, bit for bit.  HIT: the contact record's
+ *              two nearest_points and its collision_normal (an F32 record's widened)
+ *   depth      HIT: the contact record's penetration_depth, else 0
+ *   a, b       the pair's hull indices;  pair: its index in the input list
+ *   kind       GJKEPA_EVENT_*
+ *   status     the status of the record the geometry came from (the cast's; HIT: the contact's)
+ * With records == NULL a HIT event's point_a, point_b, normal, depth and status are zero.
+ * The list.  events[k] for k < min(*n_events, max_events) holds the events in ascending (time, pair) order.
+ * *n_events is the full count, also when the list is cut, and equals counts[0] + .. + counts[3]; counts[5] =
+ * HIT, START, IMPACT, UNDECIDED, BAD.  Nothing is written at or past events[max_events].  An event's rank is
+ * its position in the full order, whether or not it fits in the list.
+ * The clamp.  body_event[h] is the smallest rank among the IMPACT and UNDECIDED events that name hull h as a
+ * or b, or -1 if there is none; body_time[h] is that event's time, or 1.0 if there is none.  Both come from
+ * the full order and do not depend on max_events.  Contact at t = 0 does not clamp: HIT and START events are
+ * the contact solver's matter (gjkepa_manifold_batch), and a resting box would otherwise never move.
+ * What the clamp guarantees, and what it does not.  Body h posed at body_time[h] is at or before the time of
+ * impact of every listed pair it is in.  Against a partner that does not move (v = w = 0) the cast's
+ * certificate therefore holds and the two are at least tolerance / 2 apart.  Two moving bodies clamped to
+ * different times are not certified against each other: that policy is the caller's.
+ * Method: a key pass (each pair's flag, status and toi are read once; per-tile counts of the five classes,
+ * summed in a fixed order), a stable radix sort of (time bits, pair) (rocPRIM), and an emit pass in which rank
+ * k gathers its pair's records, writes the event, and, for an IMPACT or UNDECIDED, takes the minimum of k
+ * into body_event[a] and body_event[b]: the pass's only atomic, and a minimum does not depend on the order of
+ * arrival.  Deterministic. */
+#define GJKEPA_EVENT_HIT       1   /* in contact at t = 0 by the batch's collision byte (the cast skipped the pair) */
+#define GJKEPA_EVENT_START     2   /* within tolerance, or overlapping, at t = 0 by the cast itself */
+#define GJKEPA_EVENT_IMPACT    3   /* the hulls come within tolerance at time */
+#define GJKEPA_EVENT_UNDECIDED 4   /* the cast stopped undecided: free up to time */
+typedef struct gjkepa_event_f64 {
+    double   time;
+    double   point_a[3];
+    double   point_b[3];
+    double   normal[3];
+    double   depth;
+    int32_t  a, b;
+    int32_t  pair;
+    int8_t   kind;
+    int8_t   status;
+    int8_t   reserved[2];
+    uint32_t pad[6];
+} gjkepa_event_f64;              /* 128 bytes */
+
+/* Size in bytes of one event record (128). */
+int gjkepa_event_record_bytes(void);
+/* Bytes of device workspace for n_pairs pairs (keys, pair indices, tile counts, sort scratch; 256-byte
+ * aligned; n_hulls does not enter today); negative for a negative size or n_pairs above 2^31 - 1. */
+int64_t gjkepa_events_workspace_bytes(int64_t n_pairs, int64_t n_hulls);
+/* Device buffers, asynchronous on `stream` (hipStream_t or NULL): no allocation, no synchronisation, every
+ * launch on that stream only (a captured graph is a linear chain).
+ * pairs, cast_records: the pair list and its n_pairs cast records.  records: NULL, or the list's contact
+ * records of precision records_precision.  events: room for max_events records.  n_events, counts[5]: device
+ * int64.  body_time (double), body_event (int32): n_hulls each, both NULL to skip.  Hull indices are trusted.
+ * n_pairs == 0 gives *n_events = 0, zero counts, body_time = 1 and body_event = -1 for all n_hulls.
+ * GJKEPA_E_ARG for a null required pointer, a bad records_precision with records != NULL, a negative size, a
+ * size above 2^31 - 1 or exactly one of the two body pointers; GJKEPA_E_WORKSPACE for a workspace below
+ * gjkepa_events_workspace_bytes. */
+int gjkepa_events_device(const int32_t* pairs, int64_t n_pairs, int64_t n_hulls,
+                         const void* cast_records,
+                         const void* records, int32_t records_precision,
+                         void* events, int64_t max_events,
+                         int64_t* n_events, int64_t* counts,
+                         double* body_time, int32_t* body_event,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- whole moving step (host buffers, blocking) -------------------------------------------------
+ * gjkepa_broadphase_swept_device -> gjkepa_batch_device on the candidate list -> gjkepa_cast_rigid_batch_device
+ * with the batch's records -> gjkepa_events_device, and, when verts_out is given, gjkepa_pose_pool_device with
+ * time = body_time: the bytes those entries give when called one after the other.  The pool arguments and
+ * checks of gjkepa_broadphase_swept; body_motion, tolerance, long_radius as there; version, tol_ff, precision
+ * as for gjkepa_batch.  events: room for max_events records (the first of the list); *n_events the full count;
+ * counts (5, may be NULL) as above; *n_candidates (may be NULL) = pairs of the swept list; body_time (n_hulls,
+ * may be NULL); verts_out (may be NULL): n_vert_scalars scalars of vert_dtype, the pool posed at body_time
+ * (the scalars of no hull, and of BAD_INPUT hulls, hold the input's values). */
+int gjkepa_collide_moving(int32_t version, double tol_ff, int32_t vert_dtype, int32_t precision,
+                          const void* verts, int64_t n_vert_scalars,
+                          const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                          const double* body_motion, double tolerance, double long_radius,
+                          void* events, int64_t max_events, int64_t* n_events,
+                          int64_t* counts, int64_t* n_candidates,
+                          double* body_time, void* verts_out, int32_t device);
+
 /* ---- contact manifold (up to 4 points) of colliding pairs --------------------------------------
  * The fourth question about a pair, for the pairs a batch calls a collision: a contact patch instead of
  * the reference's one collision_point, as a solver needs for two boxes resting face to face.  It is

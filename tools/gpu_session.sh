@@ -15,6 +15,8 @@
 #   gloo2          two-rank bench rehearsal over gloo on the one GPU
 #   hull           convex-hull module: its GPU tests, H1-H3 bench lines, rocprofv3 of H1
 #   scene          broad phase + narrow phase scene bench and its rocprofv3 kernel statistics
+#   events         event pass of a moving step: a check against the restatement at 2^16 hulls, the bench lines
+#                  (tools/bench_events.py) and rocprofv3 kernel statistics of the event leg
 #   svc            resident query service: concurrent-batch cost (tools/svc_concurrent.py)
 #   c5sweep        config C5's fp64 / fp32 sweep with the >= 64-face subset (tools/c5_sweep.py)
 #   svcprobe       lone-caller latency (tools/svc_probe.py) of the product build and, from the stamps
@@ -98,6 +100,11 @@ step_hull() {
 step_scene() {
   timeout -k 10 300 python tools/bench_scene.py > $OUT/scene.json 2> $OUT/scene.err && cat $OUT/scene.json && \
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_scene -o run --output-format csv -- python3 tools/bench_scene.py --no-cpu > $OUT/prof_scene.json 2> $OUT/prof_scene.err
+}
+step_events() {
+  timeout -k 10 300 python tools/bench_events.py --hulls 65536 --check --steps 3 --warmup 1 > $OUT/events_check.json 2> $OUT/events_check.err && cat $OUT/events_check.json && \
+  timeout -k 10 400 python tools/bench_events.py > $OUT/events.json 2> $OUT/events.err && cat $OUT/events.json && \
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_events -o run --output-format csv -- python3 tools/bench_events.py --legs events --steps 5 --warmup 1 > $OUT/prof_events.json 2> $OUT/prof_events.err
 }
 step_c5sweep() { timeout -k 10 500 python tools/c5_sweep.py $((1 << 20)) $OUT/c5_fp32_sweep.json > $OUT/c5_sweep.log 2>&1 && tail -n 3 $OUT/c5_sweep.log; }
 step_svcprobe() {

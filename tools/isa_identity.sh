@@ -1,6 +1,6 @@
 #!/bin/bash
 # Device-code identity of the working tree against a parent revision, for refactors that must not move
-# the compiler's output: every GK_PART of csrc/gjkepa_kernel.hip and the hull, broad-phase, contact-list and pose kernel files
+# the compiler's output: every GK_PART of csrc/gjkepa_kernel.hip and the hull, broad-phase, swept broad-phase, contact-list and pose kernel files
 # compiled with the Makefile's flags plus --cuda-device-only -S at both, the compilation-unit symbol
 # (__hip_cuid_<hex>, a hash of the source text) masked, one sha256 pair per file.  It only diffs.
 # usage: bash tools/isa_identity.sh <parent-rev> [workdir] > profiles/rNN/isa_identity.txt
@@ -15,7 +15,7 @@ emit() {   # emit <tree> <outdir>: masked device assembly of every kernel file o
   for p in 0 1 2 3 4 5 6 7 8 9 10 11 12 13 14 15; do
     /opt/rocm/bin/hipcc $F -DGK_PART=$p "$1/$P/csrc/gjkepa_kernel.hip" -o "$2/gk_part$p.s" 2> /dev/null &
   done
-  for k in hull broadphase contacts pose; do
+  for k in hull broadphase sweep contacts pose; do
     /opt/rocm/bin/hipcc $F "$1/$P/csrc/${k}_kernel.hip" -o "$2/${k}_kernel.s" 2> /dev/null &
   done
   wait
