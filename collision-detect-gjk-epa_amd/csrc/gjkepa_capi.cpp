@@ -12,7 +12,8 @@
 // gjkepa_distance_batch(_device) for the separation-distance tiers (a counter reset and three launches on
 // the caller's stream, counters in a workspace of their own), and gjkepa_cast_batch(_device) and
 // gjkepa_manifold_batch(_device) for the linear-cast and the contact-manifold tiers (the same chain shape), as
-// does gjkepa_cast_rigid_batch(_device) for the rigid-motion cast; gjkepa_pose_pool(_device) is one launch.
+// does gjkepa_cast_rigid_batch(_device) for the rigid-motion cast; gjkepa_pose_pool(_device) is one launch,
+// as is gjkepa_mass_batch(_device); gjkepa_mass_pool chains the hull and the mass entry on the hull staging.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -35,6 +36,7 @@
 #include "contacts_kernel.h"
 #include "pose_kernel.h"
 #include "events_kernel.h"
+#include "mass_kernel.h"
 #include "capi_internal.h"
 
 namespace {
@@ -109,6 +111,7 @@ struct DeviceState {
     DevBuf d_motion;                                        // gjkepa_cast_batch / gjkepa_cast_rigid_batch / gjkepa_pose_pool staging
     DevBuf d_time, d_status;                                // gjkepa_pose_pool staging
     DevBuf m_cast, m_events, m_ws, m_n, m_time, m_rank, m_posed;   // gjkepa_collide_moving staging
+    DevBuf p_out;                                           // gjkepa_mass_batch / gjkepa_mass_pool staging (with the hull staging)
     HostBuf q_host;
 };
 
@@ -1726,6 +1729,109 @@ int gjkepa_hull_batch(int32_t vert_dtype, const void* points, int64_t n_point_sc
         if (nv && vert_idx) std::memcpy(vert_idx + cloud_off[c], hi.data() + cloud_off[c], (size_t)nv * 4);
     }
     return 0;
+}
+
+// ---- mass properties of hulls (include/gjkepa.h gjkepa_mass_*; csrc/mass_props.h) --------------
+int gjkepa_mass_record_bytes(void) { return (int)sizeof(gjkepa_mass_f64); }
+
+int gjkepa_mass_batch_device(int32_t vert_dtype, const void* points, const int64_t* cloud_off, const int32_t* cloud_cnt,
+                             int64_t n_clouds, const int64_t* face_off, const int32_t* faces, const int32_t* n_faces,
+                             const int8_t* hull_status, void* out, double* body_motion, void* stream) {
+    if (n_clouds < 0 || (vert_dtype != GJKEPA_DTYPE_F32 && vert_dtype != GJKEPA_DTYPE_F64))
+        return fail(GJKEPA_E_ARG, "bad n_clouds/dtype");
+    if (n_clouds == 0) return 0;
+    if (!points || !cloud_off || !cloud_cnt || !face_off || !faces || !n_faces || !out)
+        return fail(GJKEPA_E_ARG, "null pointer");
+    const gjkepa_mass_args a{points, cloud_off, cloud_cnt, n_clouds, face_off, faces, n_faces, hull_status, out, body_motion,
+                             num_cus_current()};
+    const hipError_t e = gjkepa_launch_mass(vert_dtype, a, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "mass kernel launch");
+}
+
+int gjkepa_mass_batch(int32_t vert_dtype, const void* points, int64_t n_point_scalars, const int64_t* cloud_off,
+                      const int32_t* cloud_cnt, int64_t n_clouds, const int64_t* face_off, int64_t n_face_slots,
+                      const int32_t* faces, const int32_t* n_faces, const int8_t* hull_status, void* out,
+                      double* body_motion, int32_t device) {
+    if (n_clouds < 0 || n_point_scalars < 0 || n_face_slots < 0 ||
+        (vert_dtype != GJKEPA_DTYPE_F32 && vert_dtype != GJKEPA_DTYPE_F64))
+        return fail(GJKEPA_E_ARG, "bad sizes/dtype");
+    if (n_clouds == 0) return 0;
+    if (!points || !cloud_off || !cloud_cnt || !face_off || !faces || !n_faces || !out)
+        return fail(GJKEPA_E_ARG, "null pointer");
+    // host-side validation of the index structure (device code trusts it), as gjkepa_hull_batch
+    for (int64_t c = 0; c < n_clouds; ++c) {
+        const int64_t n = cloud_cnt[c];
+        if (n < 4 || n > GJKEPA_HULL_MAX_POINTS) continue;      // answered with BAD_INPUT, nothing read
+        if (cloud_off[c] < 0 || cloud_off[c] + 3 * n > n_point_scalars) return fail(GJKEPA_E_ARG, "cloud outside the point pool");
+        if (face_off[c] < 0 || face_off[c] + gjkepa_hull_face_capacity((int32_t)n) > n_face_slots)
+            return fail(GJKEPA_E_ARG, "cloud's face block outside the face buffer");
+    }
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
+    const size_t nc = (size_t)n_clouds, mb = nc * GJKEPA_MOTION_DOUBLES * sizeof(double);
+    st.up_pool(vert_dtype, points, n_point_scalars, cloud_off, cloud_cnt, n_clouds);
+    st.up(d->h_foff, face_off, nc * 8);
+    st.room(d->h_faces, (size_t)n_face_slots * 12 + 12);
+    st.up(d->h_faces, faces, (size_t)n_face_slots * 12);
+    st.up(d->h_nf, n_faces, nc * 4);
+    st.up(d->h_st, hull_status, nc);
+    st.up(d->d_motion, body_motion, mb);
+    st.room(d->p_out, nc * sizeof(gjkepa_mass_f64));
+    int rc = st.failed();
+    if (rc) return rc;
+    rc = gjkepa_mass_batch_device(vert_dtype, d->verts.p, d->off.as<const int64_t>(), d->cnt.as<const int32_t>(), n_clouds,
+                                  d->h_foff.as<const int64_t>(), d->h_faces.as<const int32_t>(), d->h_nf.as<const int32_t>(),
+                                  hull_status ? d->h_st.as<const int8_t>() : nullptr, d->p_out.p,
+                                  body_motion ? d->d_motion.as<double>() : nullptr, d->stream);
+    if (rc) return rc;
+    st.down(out, d->p_out, nc * sizeof(gjkepa_mass_f64));
+    if (body_motion) st.down(body_motion, d->d_motion, mb);
+    st.sync();
+    return st.failed();
+}
+
+int gjkepa_mass_pool(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars, const int64_t* hull_off,
+                     const int32_t* hull_cnt, int64_t n_hulls, void* out, double* body_motion, int32_t device) {
+    if (n_hulls < 0 || n_vert_scalars < 0 || (vert_dtype != GJKEPA_DTYPE_F32 && vert_dtype != GJKEPA_DTYPE_F64))
+        return fail(GJKEPA_E_ARG, "bad sizes/dtype");
+    if (n_hulls == 0) return 0;
+    if (!verts || !hull_off || !hull_cnt || !out) return fail(GJKEPA_E_ARG, "null pointer");
+    int rc = check_pool(nullptr, 0, hull_off, hull_cnt, n_hulls, n_vert_scalars, GJKEPA_MAX_HULL_VERTS);
+    if (rc) return rc;
+    // the face blocks of the library's scratch, hull after hull
+    std::vector<int64_t> foff((size_t)n_hulls);
+    int64_t slots = 0;
+    for (int64_t h = 0; h < n_hulls; ++h) {
+        foff[(size_t)h] = slots;
+        slots += gjkepa_hull_face_capacity(hull_cnt[h]);
+    }
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
+    const size_t nh = (size_t)n_hulls, mb = nh * GJKEPA_MOTION_DOUBLES * sizeof(double);
+    st.up_pool(vert_dtype, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls);
+    st.up(d->h_foff, foff.data(), nh * 8);
+    st.up(d->d_motion, body_motion, mb);
+    st.room(d->h_faces, (size_t)slots * 12 + 12);
+    st.room(d->h_nf, nh * 4);
+    st.room(d->h_nv, nh * 4);
+    st.room(d->h_st, nh);
+    st.room(d->p_out, nh * sizeof(gjkepa_mass_f64));
+    if ((rc = st.failed())) return rc;
+    rc = gjkepa_hull_batch_device(vert_dtype, d->verts.p, d->off.as<const int64_t>(), d->cnt.as<const int32_t>(), n_hulls,
+                                  d->h_foff.as<const int64_t>(), d->h_faces.as<int32_t>(), d->h_nf.as<int32_t>(),
+                                  d->h_nv.as<int32_t>(), d->h_st.as<int8_t>(), nullptr, nullptr, d->stream);
+    if (rc) return rc;
+    rc = gjkepa_mass_batch_device(vert_dtype, d->verts.p, d->off.as<const int64_t>(), d->cnt.as<const int32_t>(), n_hulls,
+                                  d->h_foff.as<const int64_t>(), d->h_faces.as<const int32_t>(), d->h_nf.as<const int32_t>(),
+                                  d->h_st.as<const int8_t>(), d->p_out.p, body_motion ? d->d_motion.as<double>() : nullptr,
+                                  d->stream);
+    if (rc) return rc;
+    st.down(out, d->p_out, nh * sizeof(gjkepa_mass_f64));
+    if (body_motion) st.down(body_motion, d->d_motion, mb);
+    st.sync();
+    return st.failed();
 }
 
 // ---- device broad phase (include/gjkepa.h) --------------------------------

@@ -53,6 +53,7 @@ EXPORTS = (
     "gjkepa_manifold_batch",
     "gjkepa_broadphase_swept_workspace_bytes", "gjkepa_broadphase_swept_device", "gjkepa_broadphase_swept",
     "gjkepa_event_record_bytes", "gjkepa_events_workspace_bytes", "gjkepa_events_device", "gjkepa_collide_moving",
+    "gjkepa_mass_record_bytes", "gjkepa_mass_batch_device", "gjkepa_mass_batch", "gjkepa_mass_pool",
 )
 COMM_ID_BYTES = 128
 # workspace header word counting the park slots a gjkepa_batch_device call took (diagnostics; csrc/
@@ -103,7 +104,15 @@ EVENT64 = np.dtype([
 ])
 assert EVENT64.itemsize == 128
 event_dtype = EVENT64
-EVENTS_TILE = 4096                           # records per block of the event pass's key pass (csrc/events_kernel.h)
+# gjkepa_mass_f64 (include/gjkepa.h): one per cloud from mass_batch / mass_batch_device / mass_pool; inertia is
+# (Ixx, Iyy, Izz, Ixy, Ixz, Iyz) about com, in world axes, at unit density
+MASS64 = np.dtype([
+    ("volume", "<f8"), ("area", "<f8"), ("com", "<f8", (3,)), ("inertia", "<f8", (6,)), ("radius", "<f8"),
+    ("closure", "<f8"), ("n_faces", "<i4"), ("status", "i1"), ("flags", "i1"), ("reserved", "i1", (2,)),
+    ("pad", "<u4", (4,)),
+])
+assert MASS64.itemsize == 128
+EVENTS_TILE = 4096                         # records per block of the event pass's key pass (csrc/events_kernel.h)
 
 
 def record_dtype(precision: int) -> np.dtype:
@@ -244,6 +253,13 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.gjkepa_collide_moving.argtypes = [c_i32, c_dbl, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_dbl, c_dbl,
                                           c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32]
     lib.gjkepa_collide_moving.restype = ctypes.c_int
+    lib.gjkepa_mass_record_bytes.argtypes, lib.gjkepa_mass_record_bytes.restype = [], ctypes.c_int
+    lib.gjkepa_mass_batch_device.argtypes = [c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+    lib.gjkepa_mass_batch_device.restype = ctypes.c_int
+    lib.gjkepa_mass_batch.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32]
+    lib.gjkepa_mass_batch.restype = ctypes.c_int
+    lib.gjkepa_mass_pool.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32]
+    lib.gjkepa_mass_pool.restype = ctypes.c_int
     if path is None:
         _lib = lib
     return lib
@@ -809,6 +825,65 @@ def hull_batch_device(vert_dtype: int, points_ptr: int, cloud_off_ptr: int, clou
                                          face_off_ptr, faces_ptr, n_faces_ptr, n_verts_ptr, status_ptr,
                                          hull_verts_ptr or None, vert_idx_ptr or None, stream or None)
     _check(rc, "gjkepa_hull_batch_device")
+
+
+# ---- mass properties of hulls (include/gjkepa.h gjkepa_mass_*; csrc/mass_props.h) -----------------------
+def _mass_motion(body_motion, n: int):
+    if body_motion is None:
+        return None
+    mot = np.array(body_motion, np.float64).reshape(-1)       # a copy: the call writes the pivots into it
+    if mot.size != MOTION_DOUBLES * n:
+        raise GjkEpaError("body_motion: 9 float64 (v, w, c) per hull of the pool")
+    return mot
+
+
+def mass_batch(pool: CloudPool, hull: dict, body_motion=None, use_status: bool = True, device: int = 0):
+    """Volume, area, centre of mass, inertia (about com, world axes, unit density), bounding radius and closure
+    of every cloud's hull (host buffers, blocking): MASS64 records from the dict hull_batch returned for the
+    same pool (or faces, face_off, n_faces and status of the caller's own).  use_status False passes no hull
+    status.  body_motion: (n_clouds, 9) float64; returns (records, a copy with c = com for every OK cloud)."""
+    verts = np.ascontiguousarray(pool.verts)
+    off = np.ascontiguousarray(pool.cloud_off, np.int64)
+    cnt = np.ascontiguousarray(pool.cloud_cnt, np.int32)
+    foff = np.ascontiguousarray(hull["face_off"], np.int64)
+    faces = np.ascontiguousarray(hull["faces"], np.int32).reshape(-1, 3)
+    nf = np.ascontiguousarray(hull["n_faces"], np.int32)
+    hs = np.ascontiguousarray(hull["status"], np.int8) if use_status else None
+    if foff.size != cnt.size or nf.size != cnt.size or (hs is not None and hs.size != cnt.size):
+        raise GjkEpaError("hull: face_off, n_faces and status per cloud of the pool")
+    out = np.zeros(cnt.size, MASS64)
+    mot = _mass_motion(body_motion, cnt.size)
+    rc = load().gjkepa_mass_batch(pool.dtype_code, _ptr(verts), verts.size, _ptr(off), _ptr(cnt), cnt.size, _ptr(foff),
+                                  len(faces), _ptr(faces), _ptr(nf), None if hs is None else _ptr(hs), _ptr(out),
+                                  None if mot is None else _ptr(mot), int(device))
+    _check(rc, "gjkepa_mass_batch")
+    return out if mot is None else (out, mot.reshape(-1, MOTION_DOUBLES))
+
+
+def mass_batch_device(vert_dtype: int, points_ptr: int, cloud_off_ptr: int, cloud_cnt_ptr: int, n_clouds: int,
+                      face_off_ptr: int, faces_ptr: int, n_faces_ptr: int, hull_status_ptr: int, out_ptr: int,
+                      body_motion_ptr: int = 0, stream: int = 0) -> None:
+    """Device-resident mass properties (raw device pointers: what hull_batch_device read and wrote),
+    asynchronous on `stream`; hull_status_ptr / body_motion_ptr 0 / None: not given."""
+    rc = load().gjkepa_mass_batch_device(int(vert_dtype), points_ptr, cloud_off_ptr, cloud_cnt_ptr, int(n_clouds),
+                                         face_off_ptr, faces_ptr, n_faces_ptr, hull_status_ptr or None, out_ptr,
+                                         body_motion_ptr or None, stream or None)
+    _check(rc, "gjkepa_mass_batch_device")
+
+
+def mass_pool(pool: HullPool, body_motion=None, device: int = 0):
+    """From a narrow-phase hull pool to pivots in one call: the hull of every hull's vertices, then its mass
+    properties (MASS64 records).  body_motion: (n_hulls, 9) float64; returns (records, a copy with c = com for
+    every OK hull).  Hulls of fewer than four vertices and flat hulls come back STATUS_BAD_INPUT / _DEGENERATE."""
+    verts = np.ascontiguousarray(pool.verts)
+    off = np.ascontiguousarray(pool.hull_off, np.int64)
+    cnt = np.ascontiguousarray(pool.hull_cnt, np.int32)
+    out = np.zeros(cnt.size, MASS64)
+    mot = _mass_motion(body_motion, cnt.size)
+    rc = load().gjkepa_mass_pool(pool.dtype_code, _ptr(verts), verts.size, _ptr(off), _ptr(cnt), cnt.size, _ptr(out),
+                                 None if mot is None else _ptr(mot), int(device))
+    _check(rc, "gjkepa_mass_pool")
+    return out if mot is None else (out, mot.reshape(-1, MOTION_DOUBLES))
 
 
 def quickhull(points, device: int = 0):

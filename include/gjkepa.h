@@ -248,6 +248,79 @@ int gjkepa_hull_batch_device(int32_t vert_dtype, const void* points,
                              int32_t* n_faces, int32_t* n_verts, int8_t* status,
                              void* hull_verts, int32_t* vert_idx, void* stream);
 
+/* ---- mass properties of hulls (volume, centre of mass, inertia) ---------------------------------
+ * What a body needs besides its hull: the pivot of its motion block (the casts, the pose and the swept broad
+ * phase want c at the body's own centre, where rho is smallest), and the volume and inertia tensor a caller
+ * needs to act on an IMPACT event.  These entries reduce what gjkepa_hull_batch(_device) wrote (outward
+ * triangles over a cloud) to one record per cloud.
+ * Definition (csrc/mass_props.h is its text, for host and device; plain fp64 in the order written there).
+ * o is the point named by the first index of the cloud's first face.  It lies on the hull, so every
+ * tetrahedron (o, a, b, c) of an outward convex mesh has a signed volume >= 0 and the sums do not cancel.  Per
+ * face, with A = p_a - o, B = p_b - o, C = p_c - o:  N = (B - A) x (C - B);  d = A . (B x C);  S = (A + B) + C;
+ * the face adds d, d S_k, d (((S_i S_j + A_i A_j) + B_i B_j) + C_i C_j) for ij = xx, yy, zz, xy, xz, yz, |N| and
+ * N_k to 14 totals T.  The sum has one shape whatever the launch: 64 strided partials (partial l takes faces
+ * l, l + 64, .. in ascending order from +0.0), then P[l] = P[l] + P[l ^ s] for s = 1, 2, 4, 8, 16, 32.
+ *   volume     T0 / 6
+ *   com        o + m,  m = T[1..3] / (4 T0)
+ *   inertia    (Myy + Mzz, Mxx + Mzz, Mxx + Myy, -Mxy, -Mxz, -Myz) with M_ij = T[4..9] / 120 - volume m_i m_j:
+ *              Ixx, Iyy, Izz, Ixy, Ixz, Iyz about com, in world axes, at unit density (multiply by the density)
+ *   area       0.5 T10
+ *   closure    max|T[11..13]| / T10: 0 for a closed surface; faces of the caller's own that do not close show here
+ *   radius     sqrt(max_i |x_i - com|^2) over all points of the cloud (the maximum is attained at a hull
+ *              vertex): bit for bit the rho the swept broad phase and the rigid cast compute for the pivot c = com
+ *   n_faces    the cloud's face count
+ * status, the first rule that applies wins:
+ *   1. n outside 4 .. GJKEPA_HULL_MAX_POINTS                              GJKEPA_STATUS_BAD_INPUT
+ *   2. hull_status given and not GJKEPA_STATUS_OK                         that status, copied
+ *   3. n_faces outside 4 .. 2n - 4                                        GJKEPA_STATUS_BAD_INPUT
+ *   4. a face index outside [0, n), or a non-finite coordinate in the cloud   GJKEPA_STATUS_BAD_INPUT
+ *   5. T0 not finite or not > 0 (an inward mesh), or a result not finite  GJKEPA_STATUS_DEGENERATE
+ * A record that is not OK is zero apart from status.  Every face index is checked before a point is read
+ * through it: nothing outside the cloud is read, whatever the face buffer holds.
+ * Method: one launch, one wave per cloud (lane l holds partial l), the cloud held in LDS; no atomics, no
+ * workspace.  Deterministic. */
+typedef struct gjkepa_mass_f64 {
+    double   volume;
+    double   area;
+    double   com[3];
+    double   inertia[6];
+    double   radius;
+    double   closure;
+    int32_t  n_faces;
+    int8_t   status;
+    int8_t   flags;              /* 0 today */
+    int8_t   reserved[2];
+    uint32_t pad[4];
+} gjkepa_mass_f64;               /* 128 bytes */
+
+/* Size in bytes of one mass record (128). */
+int gjkepa_mass_record_bytes(void);
+/* Device buffers, asynchronous on `stream` (hipStream_t or NULL): no allocation, no synchronisation, every
+ * launch on that stream only (a captured graph is a linear chain); records nothing for gjkepa_launch_timing.
+ * points .. n_faces are what gjkepa_hull_batch_device read and wrote, so the two chain on one stream;
+ * hull_status (may be NULL): its status array.  out: n_clouds records.  body_motion (may be NULL): 9 doubles
+ * per cloud; an OK cloud's com is written to body_motion[9 c + 6 .. 9 c + 8] and nothing else of the block.
+ * n_clouds == 0 returns 0.  GJKEPA_E_ARG for a bad dtype, a negative count or a null required pointer. */
+int gjkepa_mass_batch_device(int32_t vert_dtype, const void* points,
+                             const int64_t* cloud_off, const int32_t* cloud_cnt, int64_t n_clouds,
+                             const int64_t* face_off, const int32_t* faces, const int32_t* n_faces,
+                             const int8_t* hull_status, void* out, double* body_motion, void* stream);
+/* Host buffers, blocking; the pool and face-buffer checks of gjkepa_hull_batch (n_point_scalars,
+ * n_face_slots).  body_motion: NULL, or 9 n_clouds doubles, in and out. */
+int gjkepa_mass_batch(int32_t vert_dtype, const void* points, int64_t n_point_scalars,
+                      const int64_t* cloud_off, const int32_t* cloud_cnt, int64_t n_clouds,
+                      const int64_t* face_off, int64_t n_face_slots, const int32_t* faces,
+                      const int32_t* n_faces, const int8_t* hull_status,
+                      void* out, double* body_motion, int32_t device);
+/* From a narrow-phase hull pool to pivots in one call (host buffers, blocking): gjkepa_hull_batch_device on
+ * the pool into face scratch of the library's, then gjkepa_mass_batch_device with the hull's status: the bytes
+ * those two give when called one after the other.  The pool arguments and checks of gjkepa_pose_pool.  Hulls of
+ * fewer than four vertices and flat hulls come back BAD_INPUT or DEGENERATE and their motion blocks are left
+ * alone.  body_motion: NULL, or 9 n_hulls doubles, in and out. */
+int gjkepa_mass_pool(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
+                     const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                     void* out, double* body_motion, int32_t device);
+
 /* ---- device broad phase -------------------------------------------------
  * Emits the candidate pair list a narrow-phase batch consumes: every pair of hulls (a < b) of a
  * pool whose bounding spheres pass the reference's own rough test,
