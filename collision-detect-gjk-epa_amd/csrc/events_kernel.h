@@ -18,3 +18,7 @@ hipError_t gjkepa_enqueue_events(const int32_t* pairs, int64_t n_pairs, int64_t 
                                  const void* records, int rec_prec, int rec_bytes, void* events, int64_t max_events,
                                  int64_t* n_events, int64_t* counts, double* body_time, int32_t* body_event, void* ws,
                                  int64_t ws_bytes, hipStream_t s, bool* ws_too_small);
+
+// enqueue the gather out[k] = manifolds[events[k].pair], k < min(*n_events, max_events), on `s` (max_events > 0)
+hipError_t gjkepa_enqueue_event_manifolds(const void* events, const int64_t* n_events, int64_t max_events,
+                                          const void* manifolds, void* out, hipStream_t s);

@@ -133,6 +133,23 @@ __global__ __launch_bounds__(BLOCK) void time_kernel(const int32_t* __restrict__
     }
 }
 
+// The manifolds of the listed events: rank k < min(*n_events, max_events) copies the 160-byte record of its
+// event's pair as ten 16-byte loads and stores, one of the ten per lane, so ten consecutive lanes read and
+// write one record's consecutive lines.
+constexpr int kManifoldQuads = (int)(sizeof(gjkepa_manifold_f64) / 16);
+static_assert(sizeof(gjkepa_manifold_f64) == 160 && kManifoldQuads == 10, "a manifold record is ten 16-byte words");
+__global__ __launch_bounds__(BLOCK) void gather_manifolds_kernel(const gjkepa_event_f64* __restrict__ events,
+                                                                 const int64_t* __restrict__ n_events, int64_t max_events,
+                                                                 const uint4* __restrict__ manifolds, uint4* __restrict__ out) {
+    const int64_t ne = *n_events;
+    const int64_t m = (ne < max_events ? ne : max_events) * kManifoldQuads;
+    for (int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x; i < m; i += (int64_t)gridDim.x * BLOCK) {
+        const int64_t k = i / kManifoldQuads;
+        const int q = (int)(i - k * kManifoldQuads);
+        out[i] = manifolds[(int64_t)events[k].pair * kManifoldQuads + q];
+    }
+}
+
 }  // namespace ev
 }  // namespace gk
 
@@ -171,6 +188,14 @@ int blocks_for(int64_t n) {
 }
 
 }  // namespace
+
+hipError_t gjkepa_enqueue_event_manifolds(const void* events, const int64_t* n_events, int64_t max_events,
+                                          const void* manifolds, void* out, hipStream_t s) {
+    using namespace gk::ev;
+    hipLaunchKernelGGL(gather_manifolds_kernel, dim3(blocks_for(max_events * kManifoldQuads)), dim3(BLOCK), 0, s,
+                       (const gjkepa_event_f64*)events, n_events, max_events, (const uint4*)manifolds, (uint4*)out);
+    return hipGetLastError();
+}
 
 int64_t gjkepa_events_ws_floor(int64_t n_pairs) { return (int64_t)layout(n_pairs, 0).total; }
 

@@ -110,7 +110,8 @@ struct DeviceState {
     DevBuf d_rec, d_out, d_ws;                              // gjkepa_distance_batch / gjkepa_cast_batch staging
     DevBuf d_motion;                                        // gjkepa_cast_batch / gjkepa_cast_rigid_batch / gjkepa_pose_pool staging
     DevBuf d_time, d_status;                                // gjkepa_pose_pool staging
-    DevBuf m_cast, m_events, m_ws, m_n, m_time, m_rank, m_posed;   // gjkepa_collide_moving staging
+    DevBuf m_cast, m_events, m_ws, m_n, m_time, m_rank, m_posed;   // gjkepa_collide_moving staging (m_cast: gjkepa_manifold_cast_batch too)
+    DevBuf m_manifold, m_patch;                             // gjkepa_collide_moving_patches staging
     DevBuf p_out;                                           // gjkepa_mass_batch / gjkepa_mass_pool staging (with the hull staging)
     HostBuf q_host;
 };
@@ -1105,6 +1106,74 @@ int gjkepa_manifold_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_
     st.room(d->d_ws, (size_t)GJKEPA_MANIFOLD_WS_BYTES);
     if ((rc = st.failed())) return rc;
     if ((rc = manifold_enqueue(staged_query(d, vert_dtype, n_pairs, records, records_precision), margin))) return rc;
+    st.down(out, d->d_out, (size_t)n_pairs * sizeof(gjkepa_manifold_f64));
+    st.sync();
+    return st.failed();
+}
+
+// ---- contact manifold at the time of impact ------------------------------------------------------
+int64_t gjkepa_manifold_cast_workspace_bytes(int64_t n_pairs) { return gjkepa_manifold_workspace_bytes(n_pairs); }
+
+}  // extern "C"
+
+namespace {
+// the contact records are optional here: their precision counts when they are given
+int manifold_cast_args_ok(int32_t vert_dtype, int64_t n_pairs, const void* records, int32_t records_precision, double margin) {
+    return pair_query_args_ok(vert_dtype, n_pairs, records != nullptr, records_precision,
+                              margin >= 0.0 && margin <= 1.7976931348623157e308, "margin is NaN, infinite or negative");
+}
+int manifold_cast_enqueue(const PairQuery& q, const double* body_motion, const void* cast_records, double margin) {
+    gjkepa_manifold_cast_args a{};
+    a.body_motion = body_motion;
+    a.cast = (const gjkepa_cast_f64*)cast_records;
+    a.margin = margin;
+    return pair_query_enqueue(a, q, "manifold at toi", gjkepa_launch_manifold_cast);
+}
+}  // namespace
+
+extern "C" {
+
+int gjkepa_manifold_cast_batch_device(int32_t vert_dtype, const void* verts, const int64_t* hull_off,
+                                      const int32_t* hull_cnt, const int32_t* pairs, int64_t n_pairs,
+                                      const double* body_motion, const void* cast_records, const void* records,
+                                      int32_t records_precision, double margin, void* out, void* workspace,
+                                      int64_t workspace_bytes, void* stream) {
+    const gjkepa_internal::Range range_("gjkepa_manifold_cast_batch_device (chain enqueue)");
+    int rc = manifold_cast_args_ok(vert_dtype, n_pairs, records, records_precision, margin);
+    if (rc) return rc;
+    if (n_pairs == 0) return 0;
+    if (!verts || !hull_off || !hull_cnt || !pairs || !body_motion || !cast_records || !out || !workspace)
+        return fail(GJKEPA_E_ARG, "null pointer");
+    return manifold_cast_enqueue(PairQuery{vert_dtype, verts, hull_off, hull_cnt, pairs, n_pairs, records, records_precision, out,
+                                           workspace, workspace_bytes, (hipStream_t)stream, 0},
+                                 body_motion, cast_records, margin);
+}
+
+int gjkepa_manifold_cast_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
+                               const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                               const int32_t* pairs, int64_t n_pairs, const double* body_motion,
+                               const void* cast_records, const void* records, int32_t records_precision,
+                               double margin, void* out, int32_t device) {
+    const gjkepa_internal::Range range_("gjkepa_manifold_cast_batch (H2D, chain, D2H)");
+    if (n_hulls < 0 || n_vert_scalars < 0) return fail(GJKEPA_E_ARG, "bad sizes");
+    int rc = manifold_cast_args_ok(vert_dtype, n_pairs, records, records_precision, margin);
+    if (rc) return rc;
+    if (n_pairs == 0) return 0;
+    if (!verts || !hull_off || !hull_cnt || !pairs || !body_motion || !cast_records || !out) return fail(GJKEPA_E_ARG, "null pointer");
+    if ((rc = check_pool(pairs, n_pairs, hull_off, hull_cnt, n_hulls, n_vert_scalars, kAnyHullCount))) return rc;
+    Stage st(device);
+    if (st.rc) return st.rc;
+    DeviceState* d = st.d;
+    st.up_pool(vert_dtype, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls, pairs, n_pairs);
+    st.up(d->d_motion, body_motion, (size_t)n_hulls * GJKEPA_MOTION_DOUBLES * sizeof(double));
+    st.up(d->m_cast, cast_records, (size_t)n_pairs * sizeof(gjkepa_cast_f64));
+    st.up(d->d_rec, records, records ? (size_t)n_pairs * (size_t)gjkepa_record_bytes(records_precision) : 0);
+    st.room(d->d_out, (size_t)n_pairs * sizeof(gjkepa_manifold_f64));
+    st.room(d->d_ws, (size_t)GJKEPA_MANIFOLD_WS_BYTES);
+    if ((rc = st.failed())) return rc;
+    if ((rc = manifold_cast_enqueue(staged_query(d, vert_dtype, n_pairs, records, records_precision),
+                                    d->d_motion.as<const double>(), d->m_cast.p, margin)))
+        return rc;
     st.down(out, d->d_out, (size_t)n_pairs * sizeof(gjkepa_manifold_f64));
     st.sync();
     return st.failed();
@@ -2126,18 +2195,25 @@ int gjkepa_collide(int32_t version, double tol_ff, int32_t vert_dtype, int32_t p
     return 0;
 }
 
-// ---- whole moving step: swept broad phase -> narrow phase -> rigid cast -> events (-> pose) -------
-int gjkepa_collide_moving(int32_t version, double tol_ff, int32_t vert_dtype, int32_t precision, const void* verts,
-                          int64_t n_vert_scalars, const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
-                          const double* body_motion, double tolerance, double long_radius, void* events,
-                          int64_t max_events, int64_t* n_events, int64_t* counts, int64_t* n_candidates,
-                          double* body_time, void* verts_out, int32_t device) {
-    const gjkepa_internal::Range range_("gjkepa_collide_moving (swept broad phase, chain, cast, events)");
+}  // extern "C"
+
+namespace {
+// ---- whole moving step: swept broad phase -> narrow phase -> rigid cast -> events (-> patches) (-> pose) ----
+// with_patches: gjkepa_collide_moving_patches, which adds the manifold at the time of impact of every candidate
+// and the gather of the listed events' records between the event pass and the pose
+int collide_moving_run(int32_t version, double tol_ff, int32_t vert_dtype, int32_t precision, const void* verts,
+                       int64_t n_vert_scalars, const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                       const double* body_motion, double tolerance, double long_radius, void* events,
+                       int64_t max_events, int64_t* n_events, int64_t* counts, int64_t* n_candidates,
+                       double* body_time, void* verts_out, bool with_patches, double margin, void* patches,
+                       int32_t device) {
     if (max_events < 0 || n_vert_scalars < 0 || !valid_enums(vert_dtype, precision))
         return fail(GJKEPA_E_ARG, "bad sizes/dtype/precision");
     int rc = sweep_args_ok(vert_dtype, n_hulls, 0, tolerance, long_radius);
     if (rc) return rc;
-    if (!n_events || (max_events > 0 && !events)) return fail(GJKEPA_E_ARG, "null pointer");
+    if (with_patches && !(margin >= 0.0 && margin <= 1.7976931348623157e308))
+        return fail(GJKEPA_E_ARG, "margin is NaN, infinite or negative");
+    if (!n_events || (max_events > 0 && (!events || (with_patches && !patches)))) return fail(GJKEPA_E_ARG, "null pointer");
     *n_events = 0;
     if (n_candidates) *n_candidates = 0;
     for (int i = 0; counts && i < 5; ++i) counts[i] = 0;
@@ -2193,6 +2269,10 @@ int gjkepa_collide_moving(int32_t version, double tol_ff, int32_t vert_dtype, in
     st.room(d->m_time, (size_t)n_hulls * 8);
     st.room(d->m_rank, (size_t)n_hulls * 4);
     if (verts_out) st.room(d->m_posed, pool_bytes);
+    if (with_patches) {
+        st.room(d->m_manifold, (size_t)ncand * sizeof(gjkepa_manifold_f64));
+        st.room(d->m_patch, (size_t)m_max * sizeof(gjkepa_manifold_f64) + 16);
+    }
     if ((rc = st.failed())) return rc;
     const auto* cand = d->b_pairs.as<const int32_t>();
     if ((rc = enqueue(version, tol_ff, vert_dtype, precision, d->verts.p, off, cnt, cand, ncand, d->out.p, d->ws.p,
@@ -2206,6 +2286,15 @@ int gjkepa_collide_moving(int32_t version, double tol_ff, int32_t vert_dtype, in
     if ((rc = gjkepa_events_device(cand, ncand, n_hulls, d->m_cast.p, d->out.p, precision, d->m_events.p, m_max, dn, dn + 1,
                                    d->m_time.as<double>(), d->m_rank.as<int32_t>(), d->m_ws.p, (int64_t)d->m_ws.cap, s)))
         return rc;
+    if (with_patches && ncand > 0 && m_max > 0) {
+        // the cast's counters are done with: the same workspace serves the manifold's
+        if ((rc = manifold_cast_enqueue(PairQuery{vert_dtype, d->verts.p, off, cnt, cand, ncand, d->out.p, precision,
+                                                  d->m_manifold.p, d->d_ws.p, (int64_t)d->d_ws.cap, s, d->num_cus},
+                                        motion, d->m_cast.p, margin)))
+            return rc;
+        const hipError_t e = gjkepa_enqueue_event_manifolds(d->m_events.p, dn, m_max, d->m_manifold.p, d->m_patch.p, s);
+        if (e != hipSuccess) return hip_fail(e, "event manifold gather launch");
+    }
     if (verts_out) {
         // the scalars the pose leaves alone (no hull's, a bad hull's) hold the input's values
         st.note(hipMemcpyAsync(d->m_posed.p, d->verts.p, pool_bytes, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync D2D");
@@ -2225,9 +2314,45 @@ int gjkepa_collide_moving(int32_t version, double tol_ff, int32_t vert_dtype, in
     const int64_t m = host_n[0] < m_max ? host_n[0] : m_max;
     if (m > 0) {
         st.down(events, d->m_events, (size_t)m * sizeof(gjkepa_event_f64));
+        if (with_patches) st.down(patches, d->m_patch, (size_t)m * sizeof(gjkepa_manifold_f64));
         st.sync();
     }
     return st.failed();
+}
+}  // namespace
+
+extern "C" {
+
+int gjkepa_collide_moving(int32_t version, double tol_ff, int32_t vert_dtype, int32_t precision, const void* verts,
+                          int64_t n_vert_scalars, const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                          const double* body_motion, double tolerance, double long_radius, void* events,
+                          int64_t max_events, int64_t* n_events, int64_t* counts, int64_t* n_candidates,
+                          double* body_time, void* verts_out, int32_t device) {
+    const gjkepa_internal::Range range_("gjkepa_collide_moving (swept broad phase, chain, cast, events)");
+    return collide_moving_run(version, tol_ff, vert_dtype, precision, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls,
+                              body_motion, tolerance, long_radius, events, max_events, n_events, counts, n_candidates,
+                              body_time, verts_out, false, 0.0, nullptr, device);
+}
+
+int gjkepa_collide_moving_patches(int32_t version, double tol_ff, int32_t vert_dtype, int32_t precision, const void* verts,
+                                  int64_t n_vert_scalars, const int64_t* hull_off, const int32_t* hull_cnt,
+                                  int64_t n_hulls, const double* body_motion, double tolerance, double long_radius,
+                                  void* events, int64_t max_events, int64_t* n_events, int64_t* counts,
+                                  int64_t* n_candidates, double* body_time, void* verts_out, double margin,
+                                  void* patches, int32_t device) {
+    const gjkepa_internal::Range range_("gjkepa_collide_moving_patches (swept broad phase, chain, cast, events, manifolds)");
+    return collide_moving_run(version, tol_ff, vert_dtype, precision, verts, n_vert_scalars, hull_off, hull_cnt, n_hulls,
+                              body_motion, tolerance, long_radius, events, max_events, n_events, counts, n_candidates,
+                              body_time, verts_out, true, margin, patches, device);
+}
+
+int gjkepa_event_manifolds_device(const void* events, const int64_t* n_events, int64_t max_events, const void* manifolds,
+                                  void* out, void* stream) {
+    if (max_events < 0 || max_events > INT32_MAX) return fail(GJKEPA_E_ARG, "bad max_events");
+    if (!n_events || (max_events > 0 && (!events || !manifolds || !out))) return fail(GJKEPA_E_ARG, "null pointer");
+    if (max_events == 0) return 0;
+    const hipError_t e = gjkepa_enqueue_event_manifolds(events, n_events, max_events, manifolds, out, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "event manifold gather launch");
 }
 
 }  // extern "C"

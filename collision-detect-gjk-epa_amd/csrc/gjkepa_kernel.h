@@ -507,6 +507,53 @@ struct gjkepa_manifold_args {
 };
 hipError_t gjkepa_launch_manifold(int tier, int vert_dtype, const gjkepa_manifold_args& a, hipStream_t s);
 
+// ---- manifold at the time of impact (gjkepa_manifold_cast_batch_device): the contact manifold's steps on
+// the two hulls posed at the pair's own toi (rigid_pose.h), the normal and the fallback point taken from the
+// pair's cast record; a pair the cast skipped as a hit is answered from its contact record, unposed, as the
+// contact manifold answers it.  The manifold tiers' shapes, pair schedule (for_each_dist_pair with the cast
+// records' filter) and workspace layout; the two motions and pose states live in the group's LDS image.
+// GJKEPA_MC_STASH: how manifold_clip.h reads a vertex.  1: the (posed) feature vertices, at most 32 per hull,
+// are written once as doubles into the group's image after step 2 and read from there; 0: the vertex is read
+// from the hull image and posed at every access.  A/B in one session (profiles/r21/ab_vert.txt, 2^18 pairs): the
+// two tie on 32-vertex hulls (0.757 against 0.751 ms) and the stash wins on mixed 8-256 hulls (0.80 against
+// 1.00 ms), where features are long and the clip reads each vertex many times: 1 ships.
+// Waves per SIMD of the tiers.  The kernel needs 204 to 205 VGPRs; at three waves (168) tiers 0 and 2 spill 51
+// to 62 of them (128 to 160 bytes of scratch).  A/B per tier (profiles/r21/ab_minw.txt, "minw t0 t1 t2"): two
+// waves everywhere is the fastest on the 32-vertex pool (0.738 ms against 0.755 with tier 0 at three, run-to-run
+// 0.0002) and level with every other setting on the mixed pool (0.789 against 0.792 to 0.805, run-to-run 0.005),
+// so unlike the contact manifold's tiers no tier takes the third wave.
+#ifndef GJKEPA_MC_STASH
+#define GJKEPA_MC_STASH 1
+#endif
+#ifndef GJKEPA_I0_MINW
+#define GJKEPA_I0_MINW 2
+#endif
+#ifndef GJKEPA_I1_MINW
+#define GJKEPA_I1_MINW 2
+#endif
+#ifndef GJKEPA_I2_MINW
+#define GJKEPA_I2_MINW 2
+#endif
+struct gjkepa_manifold_cast_args {
+    const void* verts;
+    const int64_t* hull_off;
+    const int32_t* hull_cnt;
+    const int32_t* pairs;
+    int64_t n_pairs;
+    const unsigned char* records;   // the contact records of the same pair list, or nullptr
+    int rec_stride;                 // bytes per contact record (128: fp64 fields, 64: fp32), and the offset of
+    int rec_hit_off;                // its collision byte (the status byte is two further on)
+    const gjkepa_cast_f64* cast;    // the cast records of the same pair list (required)
+    const double* body_motion;      // GJKEPA_MOTION_DOUBLES per hull of the pool: the blocks the cast ran with
+    double margin;                  // thickness of the two features (finite, >= 0)
+    uint32_t* ctr;                  // this launch's chunk counter (zero at launch)
+    void* out;                      // gjkepa_manifold_f64 records
+    int grid;                       // <= 0: occupancy x CUs
+    int num_cus;
+    static constexpr int kSkipFlag = GJKEPA_MANIFOLD_NO_HIT;
+};
+hipError_t gjkepa_launch_manifold_cast(int tier, int vert_dtype, const gjkepa_manifold_cast_args& a, hipStream_t s);
+
 hipError_t gjkepa_launch_gjk(int tier, int vert_dtype, int precision, const gjkepa_gjk_args& a, hipStream_t s);
 hipError_t gjkepa_launch_epa(int tier, int vert_dtype, int precision, const gjkepa_epa_args& a, hipStream_t s);
 // contact tiers take the same argument block (route_code = GJKEPA_ROUTE_CT0 + tier; next_code unused)

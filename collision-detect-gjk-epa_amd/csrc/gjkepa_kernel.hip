@@ -38,14 +38,17 @@
 #else
 #define GK_IN(p) 1
 #endif
-#if GK_IN(12) || GK_IN(14)
-#include "dist_simplex.h"       // the distance GJK's simplex arithmetic (host and device); part 14: the record helpers' constants
+#if GK_IN(12) || GK_IN(14) || GK_IN(16)
+#include "dist_simplex.h"       // the distance GJK's simplex arithmetic (host and device); parts 14, 16: the record helpers' constants
 #endif
 #if GK_IN(13) || GK_IN(15)
 #include "cast_advance.h"       // the linear and the rigid-motion cast: conservative advancement over the distance GJK
 #endif
-#if GK_IN(14)
+#if GK_IN(14) || GK_IN(16)
 #include "manifold_clip.h"      // the contact manifold's plane geometry (host and device)
+#endif
+#if GK_IN(16)
+#include "rigid_pose.h"         // the path the rigid cast certified: the hulls at a pair's time of impact
 #endif
 
 namespace gk {
@@ -3114,7 +3117,7 @@ __global__ __launch_bounds__(64) void ws_reset_kernel(uint32_t* ws, int n32, uin
 }
 #endif  // GK_IN(0)
 
-#if GK_IN(12) || GK_IN(13) || GK_IN(14) || GK_IN(15)
+#if GK_IN(12) || GK_IN(13) || GK_IN(14) || GK_IN(15) || GK_IN(16)
 // ---------------------------------------------------------------- separation distance
 // gjkepa_distance_f64: 13 doubles (distance, point_a, point_b, normal, lambda), code[3], the four
 // int8 fields, iters, pad (the cast record: steps).  Its 16 8-byte words are stored from registers, word j by group lane j % G.
@@ -3181,8 +3184,32 @@ DEV bool manifold_hit(const unsigned char* records, int64_t p, int stride, int h
 // filter; 2^22 C4 pairs 16.1 -> 10.5 ms).  ARGS: gjkepa_dist_args, or the casts' gjkepa_cast_args /
 // gjkepa_cast_rigid_args (the same fields and their own skip flag).  HITS (the contact manifold, gjkepa_manifold_args): the filter
 // is turned round, the groups get the usable hits and the lane answers every other pair with NO_HIT.
-template <int G, int CAP, int TIER, bool HITS = false, typename ARGS, typename F>
+// CASTS (the manifold at the time of impact, gjkepa_manifold_cast_args): the lane classifies the pair by its
+// cast record (manifold_cast_class) and answers every pair that is not computed.
+[[maybe_unused]] constexpr int kPairsSkipHits = 0, kPairsHits = 1, kPairsCasts = 2;
+#if GK_IN(16)
+// What pair p's cast record (and, for a pair the cast skipped, its contact record) asks of the manifold at the
+// time of impact, by the rules of include/gjkepa.h in their order, the hull counts being valid.
+constexpr int kMcBad = 0, kMcNoHit = 1, kMcContact = 2, kMcCast = 3;
+template <typename ARGS> DEV int manifold_cast_class(const ARGS& a, int64_t p) {
+    const gjkepa_cast_f64& r = a.cast[p];
+    const int status = r.status, flags = r.flags;
+    if (flags & GJKEPA_CAST_SKIPPED) {
+        V3<double> n;
+        return a.records && manifold_hit(a.records, p, a.rec_stride, a.rec_hit_off, n) ? kMcContact : kMcNoHit;
+    }
+    if (status == GJKEPA_STATUS_BAD_INPUT) return kMcBad;
+    if (status == GJKEPA_STATUS_CAST_MAXITER) return kMcNoHit;
+    if (flags & (GJKEPA_CAST_IMPACT | GJKEPA_CAST_START)) {
+        const double x = r.normal[0], y = r.normal[1], z = r.normal[2];
+        if (isfinite(x) && isfinite(y) && isfinite(z) && (x != 0.0 || y != 0.0 || z != 0.0)) return kMcCast;
+    }
+    return kMcNoHit;
+}
+#endif
+template <int G, int CAP, int TIER, int FILTER = kPairsSkipHits, typename ARGS, typename F>
 DEV void for_each_dist_pair(const Grp<G>& grp, const ARGS& a, F&& f) {
+    constexpr bool HITS = FILTER == kPairsHits;
     constexpr int LO = TIER == 0 ? 0 : TIER == 1 ? GJKEPA_G0_G * GJKEPA_G0_K : GJKEPA_G1_G * GJKEPA_G1_K;
     static_assert(LO < CAP, "tier brackets ascend");
     const Units U(a.n_pairs, tail_unit<G, (64 / G > 8 ? 64 / G : 8)>(a.n_pairs));
@@ -3199,6 +3226,18 @@ DEV void for_each_dist_pair(const Grp<G>& grp, const ARGS& a, F&& f) {
             const int64_t p = p0 + grp.lane;
             const int na = a.hull_cnt[a.pairs[2 * p]], nb = a.hull_cnt[a.pairs[2 * p + 1]];
             const int nmax = na > nb ? na : nb;
+#if GK_IN(16)
+            if constexpr (FILTER == kPairsCasts) {
+                if (na < 1 || nb < 1 || na > GJKEPA_MAX_HULL_VERTS || nb > GJKEPA_MAX_HULL_VERTS) {
+                    if (TIER == 0) store_manifold_empty(a.out, p, GJKEPA_STATUS_BAD_INPUT, 0);
+                } else if (nmax > LO && nmax <= CAP) {
+                    const int cls = manifold_cast_class(a, p);
+                    if (cls == kMcBad) store_manifold_empty(a.out, p, GJKEPA_STATUS_BAD_INPUT, 0);
+                    else if (cls == kMcNoHit) store_manifold_empty(a.out, p, GJKEPA_STATUS_OK, ARGS::kSkipFlag);
+                    else take = true;
+                }
+            } else
+#endif
             if constexpr (HITS) {
                 V3<double> n;
                 if (na < 1 || nb < 1 || na > GJKEPA_MAX_HULL_VERTS || nb > GJKEPA_MAX_HULL_VERTS) {
@@ -3286,7 +3325,7 @@ __global__ __launch_bounds__(64, MINW) void dist_kernel(const gjkepa_dist_args a
     for_each_dist_pair<G, G * K, TIER>(grp, a, body);
 }
 #endif  // GK_IN(12)
-#endif  // GK_IN(12) || GK_IN(13) || GK_IN(14) || GK_IN(15)
+#endif  // GK_IN(12) || GK_IN(13) || GK_IN(14) || GK_IN(15) || GK_IN(16)
 
 #if GK_IN(13)
 // ---------------------------------------------------------------- linear cast
@@ -3477,7 +3516,7 @@ __global__ __launch_bounds__(64, MINW) void cast_rigid_kernel(const gjkepa_cast_
 }
 #endif  // GK_IN(15)
 
-#if GK_IN(14)
+#if GK_IN(14) || GK_IN(16)
 // ---------------------------------------------------------------- contact manifold
 // Manifold kernel of tier TIER: the distance tiers' shapes and schedule, one group per usable hit.  The
 // heights, the feature membership and the members' ranks (steps 1 and 2 of the definition,
@@ -3545,7 +3584,9 @@ template <int G, int K> DEV int manifold_feature(const Grp<G>& grp, const double
     }
     return cnt;
 }
+#endif  // GK_IN(14) || GK_IN(16)
 
+#if GK_IN(14)
 template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
 __global__ __launch_bounds__(64, MINW) void manifold_kernel(const gjkepa_manifold_args a) {
     using T = double;
@@ -3617,9 +3658,181 @@ __global__ __launch_bounds__(64, MINW) void manifold_kernel(const gjkepa_manifol
         store_manifold<G>(a.out, pair, gl, w);
         __builtin_amdgcn_wave_barrier();
     };
-    for_each_dist_pair<G, G * K, TIER, true>(grp, a, body);
+    for_each_dist_pair<G, G * K, TIER, kPairsHits>(grp, a, body);
 }
 #endif  // GK_IN(14)
+
+#if GK_IN(16)
+// ---------------------------------------------------------------- manifold at the time of impact
+// The manifold kernel on other inputs (include/gjkepa.h gjkepa_manifold_cast_batch_device): a pair whose cast
+// record is an IMPACT or a START gets the manifold of the two hulls posed at the record's toi by rigid_pose.h,
+// along n = -normal of the cast record, the fallback point its point_a; a pair the cast skipped as a hit gets
+// the contact manifold of its contact record on the unposed hulls, the manifold kernel's arithmetic on the
+// manifold kernel's inputs, so the same bytes.  The hull image stays unposed in the storage dtype.  Heights
+// and feature membership are lane-parallel as there, each lane posing its own K vertices per hull; the two
+// motions and pose states are group-uniform values in the group's image, as in the rigid cast.
+// GJKEPA_MC_STASH 1: after step 2 the vertices of the two (decimated) features, at most 32 per hull, are
+// written once as doubles (posed, or widened) into the image, slot k = the feature's k-th vertex;
+// manifold_clip.h then works on slots, and the codes it leaves are turned back into vertex indices through
+// the feature lists.  0: manifold_clip.h reads a vertex from the hull image and poses it at every access.
+// Both run pose_point's text once per value they use, so the bytes agree.
+template <typename TH, int G, int K> struct McLds {
+    MfLds<TH, G, K> mf;
+    gkd::Motion mot[2];             // hull A's and hull B's motion
+    gkd::PoseState st[2];           // their pose at the pair's toi
+#if GJKEPA_MC_STASH
+    gkm::D3 pv[2][gkm::kMaxFeature];   // the features' vertices as the clip reads them
+#endif
+};
+template <typename C, typename L_t> struct McMem {
+    const C& c;
+    L_t& L;
+    bool posed;
+#if GJKEPA_MC_STASH
+    DEV gkm::D3 vert(int h, int k) const { return L.pv[h][k]; }
+    DEV int feat(int, int k) const { return k; }
+#else
+    DEV gkm::D3 vert(int h, int i) const {
+        const auto v = c.raw(h, i);
+        const gkd::D3 p = gkd::mk((double)v.x, (double)v.y, (double)v.z);
+        if (!posed) return gkm::mk(p.x, p.y, p.z);
+        const gkd::D3 q = gkd::pose_point(L.st[h], L.mot[h].c, p);
+        return gkm::mk(q.x, q.y, q.z);
+    }
+    DEV int feat(int h, int k) const { return L.mf.feat[h][k]; }
+#endif
+    DEV int foot(int h, int k) const { return L.mf.foot[h][k]; }
+    DEV void set_foot(int h, int k, int i) { L.mf.foot[h][k] = (uint8_t)i; }
+    DEV double sqrt(double x) const { return tsqrt(x); }
+};
+
+template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
+__global__ __launch_bounds__(64, MINW) void manifold_cast_kernel(const gjkepa_manifold_cast_args a) {
+    using T = double;
+    using L_t = McLds<TIn, G, K>;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const Grp<G> grp;
+    L_t& L = *reinterpret_cast<L_t*>(smem + lds_stride<L_t, G>() * (grp.lane / G));
+    const int gl = grp.gl;
+    const TIn* verts = (const TIn*)a.verts;
+    auto body = [&](int64_t pair, const PairMeta& pm) {      // a pair of this tier with valid counts that is computed
+        using C = Ctx<T, TIn, G, K, 0, 0, LH>;
+        C c{L.mf.hull, grp};
+        c.na = grp.uni(pm.na);
+        c.nb = grp.uni(pm.nb);
+        const gjkepa_cast_f64& cr = a.cast[pair];
+        const bool posed = grp.unib((cr.flags & GJKEPA_CAST_SKIPPED) == 0);
+        V3<T> n;
+        gkm::D3 cp;
+        bool bad = false;
+        if (posed) {
+            // the cast's normal points from B to A, the manifold's from A into B
+            n = vmk<T>(-cr.normal[0], -cr.normal[1], -cr.normal[2]);
+            cp = gkm::mk(cr.point_a[0], cr.point_a[1], cr.point_a[2]);
+            const double toi = cr.toi;
+            const double* ma = a.body_motion + (int64_t)GJKEPA_MOTION_DOUBLES * a.pairs[2 * pair];
+            const double* mb = a.body_motion + (int64_t)GJKEPA_MOTION_DOUBLES * a.pairs[2 * pair + 1];
+            double* mot = reinterpret_cast<double*>(&L.mot[0]);
+            for (int j = gl; j < 2 * GJKEPA_MOTION_DOUBLES; j += G) {
+                const double x = j < GJKEPA_MOTION_DOUBLES ? ma[j] : mb[j - GJKEPA_MOTION_DOUBLES];
+                bad = bad || !isfinite(x);
+                mot[j] = x;
+            }
+            bad = grp.any(bad) || !(toi >= 0.0 && toi <= 1.0);
+            __builtin_amdgcn_wave_barrier();
+            if (!bad) {
+                L.st[0] = gkd::pose_state(L.mot[0].v, L.mot[0].w, toi);
+                L.st[1] = gkd::pose_state(L.mot[1].v, L.mot[1].w, toi);
+            }
+        } else {
+            manifold_hit(a.records, pair, a.rec_stride, a.rec_hit_off, n);
+            const unsigned char* rec = a.records + pair * (int64_t)a.rec_stride;
+            if (a.rec_stride == (int)sizeof(gjkepa_contact_f64)) {
+                const double* d = reinterpret_cast<const double*>(rec);
+                cp = gkm::mk(d[4], d[5], d[6]);
+            } else {
+                const float* d = reinterpret_cast<const float*>(rec);
+                cp = gkm::mk((double)d[4], (double)d[5], (double)d[6]);
+            }
+        }
+        if (load_hulls(c, verts + pm.oa, verts + pm.ob) || bad) {
+            if (gl == 0) store_manifold_empty(a.out, pair, GJKEPA_STATUS_BAD_INPUT, 0);
+            __builtin_amdgcn_wave_barrier();
+            return;
+        }
+        auto at = [&](int h, V3<T> v) {
+            if (!posed) return v;
+            const gkd::D3 q = gkd::pose_point(L.st[h], L.mot[h].c, gkd::mk(v.x, v.y, v.z));
+            return vmk<T>(q.x, q.y, q.z);
+        };
+        // step 1: heights (the slots past a hull's count hold its vertex 0 again: no mask)
+        T ta[K], tb[K];
+        T va = -Tol<T>::BIG, vb = Tol<T>::BIG;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const V3<T> p = at(0, c.AV(k)), q = at(1, c.BV(k));
+            ta[k] = n.x * p.x + n.y * p.y + n.z * p.z;
+            tb[k] = n.x * q.x + n.y * q.y + n.z * q.z;
+            va = red_max(ta[k], va);
+            vb = red_min(tb[k], vb);
+        }
+        const T hA = gmax<G>(va) + T(0), hB = gmin<G>(vb) + T(0);     // -0 -> +0
+        // step 2: features
+        const int fa = manifold_feature<G, K>(grp, ta, c.na, hA - a.margin, false, L.mf.feat[0]);
+        const int fb = manifold_feature<G, K>(grp, tb, c.nb, hB + a.margin, true, L.mf.feat[1]);
+        __builtin_amdgcn_wave_barrier();
+        const int ka = gkm::decimated_count(fa), kb = gkm::decimated_count(fb);
+#if GJKEPA_MC_STASH
+        for (int k = gl; k < ka; k += G) {
+            const V3<T> v = at(0, c.A(L.mf.feat[0][k]));
+            L.pv[0][k] = gkm::mk(v.x, v.y, v.z);
+        }
+        for (int k = gl; k < kb; k += G) {
+            const V3<T> v = at(1, c.B(L.mf.feat[1][k]));
+            L.pv[1][k] = gkm::mk(v.x, v.y, v.z);
+        }
+        __builtin_amdgcn_wave_barrier();
+#endif
+        // steps 3 to 8
+        McMem<C, L_t> mem{c, L, posed};
+        const gkm::Patch p = gkm::clip_manifold(mem, gkm::mk(n.x, n.y, n.z), hA, ka, kb, cp);
+        const int flags = p.flags | ((fa > gkm::kMaxFeature || fb > gkm::kMaxFeature) ? GJKEPA_MANIFOLD_DECIMATED : 0) |
+                          (posed ? GJKEPA_MANIFOLD_AT_TOI : 0);
+        uint32_t code[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            code[k] = p.code[k];
+#if GJKEPA_MC_STASH
+            // a slot of either feature back to its vertex index (0xFFFF: no vertex of that hull)
+            const uint32_t sa = code[k] & 0xffffu, sb = code[k] >> 16;
+            const uint32_t ia = sa == gkm::kNoVert ? sa : (uint32_t)L.mf.feat[0][sa & (gkm::kMaxFeature - 1)];
+            const uint32_t ib = sb == gkm::kNoVert ? sb : (uint32_t)L.mf.feat[1][sb & (gkm::kMaxFeature - 1)];
+            code[k] = ia | (ib << 16);
+#endif
+        }
+        uint64_t w[20];
+        w[0] = __builtin_bit_cast(uint64_t, hA - hB);
+        w[1] = __builtin_bit_cast(uint64_t, n.x);
+        w[2] = __builtin_bit_cast(uint64_t, n.y);
+        w[3] = __builtin_bit_cast(uint64_t, n.z);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            w[4 + 3 * k] = __builtin_bit_cast(uint64_t, p.pt[k].x);
+            w[5 + 3 * k] = __builtin_bit_cast(uint64_t, p.pt[k].y);
+            w[6 + 3 * k] = __builtin_bit_cast(uint64_t, p.pt[k].z);
+        }
+        w[16] = (uint64_t)code[0] | ((uint64_t)code[1] << 32);
+        w[17] = (uint64_t)code[2] | ((uint64_t)code[3] << 32);
+        w[18] = (uint64_t)(uint32_t)(fa & 0xffff) | ((uint64_t)(uint32_t)(fb & 0xffff) << 16) |
+                ((uint64_t)((uint32_t)(p.n & 0xff) | ((uint32_t)GJKEPA_STATUS_OK << 8) | ((uint32_t)(flags & 0xff) << 16)) << 32);
+        w[19] = __builtin_bit_cast(uint64_t, p.area);
+        __builtin_amdgcn_wave_barrier();
+        store_manifold<G>(a.out, pair, gl, w);
+        __builtin_amdgcn_wave_barrier();
+    };
+    for_each_dist_pair<G, G * K, TIER, kPairsCasts>(grp, a, body);
+}
+#endif  // GK_IN(16)
 
 }  // namespace gk
 
@@ -3628,7 +3841,8 @@ __global__ __launch_bounds__(64, MINW) void manifold_kernel(const gjkepa_manifol
 // only its own kernels so the parts compile in parallel: 0 = chain reset, query service and the launch
 // dispatchers, 1 = one-wave query path (fp64 compute), 2 = GJK tiers, 3 = contact tiers, 4 + t = EPA
 // tier t, 10 = one-wave query path (fp32 compute), 11 = fp32 redo, 12 = separation distance tiers,
-// 13 = linear cast tiers, 14 = contact manifold tiers, 15 = rigid-motion cast tiers.
+// 13 = linear cast tiers, 14 = contact manifold tiers, 15 = rigid-motion cast tiers, 16 = the tiers of the
+// manifold at the time of impact.
 // Without GK_PART (diagnostic variant builds) one object holds every part.  The non-template kernels
 // (chain reset, query service) are defined in part 0 only.
 // the one-wave query path in fp32 compute (part 10)
@@ -3834,7 +4048,7 @@ hipError_t gjkepa_launch_gjk(int tier, int vert_dtype, int precision, const gjke
 
 #endif
 
-#if GK_IN(12) || GK_IN(13) || GK_IN(14) || GK_IN(15)
+#if GK_IN(12) || GK_IN(13) || GK_IN(14) || GK_IN(15) || GK_IN(16)
 namespace {
 // The distance, cast and manifold tiers launch alike, on GJK tier t's group shape.  FAM names the kernel
 // family: FAM::kernel<TIn, G, K, MINW, LH, TIER>, its waves per SIMD FAM::minw[tier] and a group's LDS
@@ -3897,6 +4111,21 @@ struct ManifoldTiers {
 hipError_t gjkepa_launch_manifold(int tier, int vert_dtype, const gjkepa_manifold_args& a, hipStream_t s) {
     return vert_dtype == GJKEPA_DTYPE_F32 ? pair_tier_any<ManifoldTiers, float>(tier, a, s)
                                           : pair_tier_any<ManifoldTiers, double>(tier, a, s);
+}
+#endif
+
+#if GK_IN(16)
+namespace {
+struct ManifoldCastTiers {
+    static constexpr int minw[3] = {GJKEPA_I0_MINW, GJKEPA_I1_MINW, GJKEPA_I2_MINW};
+    template <typename TIn, int G, int K, int MINW, bool LH, int TIER>
+    static constexpr auto kernel = gk::manifold_cast_kernel<TIn, G, K, MINW, LH, TIER>;
+    template <typename TIn, int G, int K> using Image = gk::McLds<TIn, G, K>;
+};
+}  // namespace
+hipError_t gjkepa_launch_manifold_cast(int tier, int vert_dtype, const gjkepa_manifold_cast_args& a, hipStream_t s) {
+    return vert_dtype == GJKEPA_DTYPE_F32 ? pair_tier_any<ManifoldCastTiers, float>(tier, a, s)
+                                          : pair_tier_any<ManifoldCastTiers, double>(tier, a, s);
 }
 #endif
 

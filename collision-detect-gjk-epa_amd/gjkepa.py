@@ -27,6 +27,7 @@ DIST_OVERLAP, DIST_HIT, DIST_FAR = 1, 2, 4   # distance record flag bits
 STATUS_CAST_MAXITER = 6                      # cast records only (gjkepa_cast_batch)
 CAST_IMPACT, CAST_START, CAST_SKIPPED = 1, 2, 4   # cast record flag bits (a miss has none)
 MANIFOLD_NO_HIT, MANIFOLD_DECIMATED, MANIFOLD_FALLBACK = 1, 2, 4   # manifold record flag bits
+MANIFOLD_AT_TOI = 8                          # built from a cast record, on the hulls posed at its toi (manifold_cast_batch)
 MANIFOLD_MAX_FEATURE = 32                    # feature vertices used per hull (gjkepa_manifold_batch)
 DTYPE_F32, DTYPE_F64 = 0, 1
 PREC_F32, PREC_F64 = 0, 1
@@ -54,6 +55,8 @@ EXPORTS = (
     "gjkepa_broadphase_swept_workspace_bytes", "gjkepa_broadphase_swept_device", "gjkepa_broadphase_swept",
     "gjkepa_event_record_bytes", "gjkepa_events_workspace_bytes", "gjkepa_events_device", "gjkepa_collide_moving",
     "gjkepa_mass_record_bytes", "gjkepa_mass_batch_device", "gjkepa_mass_batch", "gjkepa_mass_pool",
+    "gjkepa_manifold_cast_workspace_bytes", "gjkepa_manifold_cast_batch_device", "gjkepa_manifold_cast_batch",
+    "gjkepa_event_manifolds_device", "gjkepa_collide_moving_patches",
 )
 COMM_ID_BYTES = 128
 # workspace header word counting the park slots a gjkepa_batch_device call took (diagnostics; csrc/
@@ -144,7 +147,8 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib = ctypes.CDLL(p)
     c_i32, c_i64, c_dbl, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
     # the size queries: *_workspace_bytes(n_pairs) -> int64, *_record_bytes(void) -> int
-    for q in ("gjkepa", "gjkepa_distance", "gjkepa_cast", "gjkepa_cast_rigid", "gjkepa_manifold", "gjkepa_compact"):
+    for q in ("gjkepa", "gjkepa_distance", "gjkepa_cast", "gjkepa_cast_rigid", "gjkepa_manifold", "gjkepa_manifold_cast",
+              "gjkepa_compact"):
         fn = getattr(lib, q + "_workspace_bytes")
         fn.argtypes, fn.restype = [c_i64], c_i64
     for q in ("gjkepa_distance", "gjkepa_cast", "gjkepa_manifold"):
@@ -245,6 +249,17 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.gjkepa_manifold_batch_device.restype = ctypes.c_int
     lib.gjkepa_manifold_batch.argtypes = lib.gjkepa_distance_batch.argtypes
     lib.gjkepa_manifold_batch.restype = ctypes.c_int
+    lib.gjkepa_manifold_cast_batch_device.argtypes = [c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_dbl,
+                                                      c_vp, c_vp, c_i64, c_vp]
+    lib.gjkepa_manifold_cast_batch_device.restype = ctypes.c_int
+    lib.gjkepa_manifold_cast_batch.argtypes = [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32,
+                                               c_dbl, c_vp, c_i32]
+    lib.gjkepa_manifold_cast_batch.restype = ctypes.c_int
+    lib.gjkepa_event_manifolds_device.argtypes = [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]
+    lib.gjkepa_event_manifolds_device.restype = ctypes.c_int
+    lib.gjkepa_collide_moving_patches.argtypes = [c_i32, c_dbl, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_dbl,
+                                                  c_dbl, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_vp, c_i32]
+    lib.gjkepa_collide_moving_patches.restype = ctypes.c_int
     lib.gjkepa_event_record_bytes.argtypes, lib.gjkepa_event_record_bytes.restype = [], ctypes.c_int
     lib.gjkepa_events_workspace_bytes.argtypes, lib.gjkepa_events_workspace_bytes.restype = [c_i64, c_i64], c_i64
     lib.gjkepa_events_device.argtypes = [c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
@@ -669,6 +684,54 @@ def manifold_batch_device(vert_dtype: int, verts_ptr: int, hull_off_ptr: int, hu
     _check(rc, "gjkepa_manifold_batch_device")
 
 
+# ---- contact manifold at the time of impact (include/gjkepa.h gjkepa_manifold_cast_*) -------------------
+def manifold_cast_workspace_bytes(n_pairs: int) -> int:
+    b = int(load().gjkepa_manifold_cast_workspace_bytes(int(n_pairs)))
+    if b < 0:
+        raise GjkEpaError("gjkepa_manifold_cast_workspace_bytes: bad arguments")
+    return b
+
+
+def _cast_records_arg(cast_records, n_pairs: int) -> np.ndarray:
+    cast = np.ascontiguousarray(cast_records)
+    if cast.dtype != CAST64 or cast.shape != (n_pairs,):
+        raise GjkEpaError("cast_records: one CAST64 record per pair")
+    return cast
+
+
+def manifold_cast_batch(pool: HullPool, body_motion, cast_records, margin: float, records: np.ndarray | None = None,
+                        device: int = 0) -> np.ndarray:
+    """Contact manifold of every pair of the pool at its own time of impact (host buffers, blocking); returns
+    MANIFOLD64 records.  cast_records: the pool's CAST64 records from cast_rigid_batch; body_motion: the
+    (n_hulls, 9) blocks that cast ran with.  An IMPACT or START pair gets the manifold of the two hulls posed at
+    its toi along the cast's normal, with flag MANIFOLD_AT_TOI; a pair the cast skipped as a hit gets what
+    manifold_batch gives it from `records` (MANIFOLD_NO_HIT without records); a miss or an undecided pair
+    MANIFOLD_NO_HIT.  margin as for manifold_batch."""
+    out = np.zeros(pool.n_pairs, dtype=MANIFOLD64)
+    keep, pool_args = _pool_args(pool)
+    mot = _motion_arg(pool, body_motion)
+    cast = _cast_records_arg(cast_records, pool.n_pairs)
+    records, rec_ptr, rec_prec = _records_arg(records, pool.n_pairs)
+    rc = load().gjkepa_manifold_cast_batch(pool.dtype_code, *pool_args, _ptr(mot), _ptr(cast), rec_ptr, rec_prec,
+                                           float(margin), _ptr(out), int(device))
+    _check(rc, "gjkepa_manifold_cast_batch")
+    return out
+
+
+def manifold_cast_batch_device(vert_dtype: int, verts_ptr: int, hull_off_ptr: int, hull_cnt_ptr: int, pairs_ptr: int,
+                               n_pairs: int, body_motion_ptr: int, cast_records_ptr: int, records_ptr: int,
+                               records_precision: int, margin: float, out_ptr: int, ws_ptr: int, ws_bytes: int,
+                               stream: int = 0) -> None:
+    """Device-resident manifold at the time of impact (raw device pointers), asynchronous on `stream`.  Chain it
+    after cast_rigid_batch_device with that call's output as the cast records; records_ptr 0 / None: no contact
+    records."""
+    rc = load().gjkepa_manifold_cast_batch_device(int(vert_dtype), verts_ptr, hull_off_ptr, hull_cnt_ptr, pairs_ptr,
+                                                  int(n_pairs), body_motion_ptr or None, cast_records_ptr or None,
+                                                  records_ptr or None, int(records_precision), float(margin), out_ptr,
+                                                  ws_ptr, int(ws_bytes), stream or None)
+    _check(rc, "gjkepa_manifold_cast_batch_device")
+
+
 # ---- multi-GPU (SURVEY.md §8 row e; include/gjkepa.h gjkepa_shard_range / _batch_multi / _comm_*) ------
 def shard_range(n_pairs: int, world: int, rank: int) -> tuple[int, int]:
     """(first, count): the contiguous shard of pairs `rank` of `world` owns (the library's rule)."""
@@ -1087,6 +1150,48 @@ def collide_moving(pool: HullPool, body_motion, tolerance: float, long_radius: f
         if n <= cap or max_events is not None:
             return {"events": ev[:min(n, cap)], "n_events": n, "counts": counts, "n_candidates": int(ncand[0]),
                     "body_time": btime, "posed": HullPool(posed, pool.hull_off, pool.hull_cnt, pool.pairs) if pose else None}
+        cap = n
+
+
+def event_manifolds_device(events_ptr: int, n_events_ptr: int, max_events: int, manifolds_ptr: int, out_ptr: int,
+                           stream: int = 0) -> None:
+    """out[k] = manifolds[events[k].pair] for k < min(*n_events, max_events) (raw device pointers; n_events a
+    device int64), asynchronous on `stream`: the patches of an event list from the pair list's manifold records."""
+    rc = load().gjkepa_event_manifolds_device(events_ptr or None, n_events_ptr or None, int(max_events),
+                                              manifolds_ptr or None, out_ptr or None, stream or None)
+    _check(rc, "gjkepa_event_manifolds_device")
+
+
+def collide_moving_patches(pool: HullPool, body_motion, tolerance: float, margin: float, long_radius: float = float("inf"),
+                           version: int = 2, tol_ff: float = 1.0, precision: int = PREC_F64,
+                           max_events: int | None = None, pose: bool = False, device: int = 0):
+    """collide_moving with a contact patch per event: the dict of collide_moving plus patches (MANIFOLD64, one per
+    listed event): a HIT event's contact manifold, a START or IMPACT event's manifold at its time
+    (MANIFOLD_AT_TOI), MANIFOLD_NO_HIT for an UNDECIDED event.  margin as for manifold_batch."""
+    lib = load()
+    verts = np.ascontiguousarray(pool.verts)
+    off = np.ascontiguousarray(pool.hull_off, np.int64)
+    cnt = np.ascontiguousarray(pool.hull_cnt, np.int32)
+    mot = _motion_arg(pool, body_motion)
+    cap = max_events if max_events is not None else max(4 * cnt.size, 1024)
+    while True:
+        ev = np.zeros(max(cap, 1), EVENT64)
+        patches = np.zeros(max(cap, 1), MANIFOLD64)
+        ne, ncand, counts = np.zeros(1, np.int64), np.zeros(1, np.int64), np.zeros(5, np.int64)
+        btime = np.zeros(cnt.size)
+        posed = verts.copy() if pose else None
+        rc = lib.gjkepa_collide_moving_patches(int(version), float(tol_ff), pool.dtype_code, int(precision), _ptr(verts),
+                                               verts.size, _ptr(off), _ptr(cnt), cnt.size, _ptr(mot), float(tolerance),
+                                               float(long_radius), _ptr(ev), cap, _ptr(ne), _ptr(counts), _ptr(ncand),
+                                               _ptr(btime), _ptr(posed) if pose else None, float(margin), _ptr(patches),
+                                               int(device))
+        _check(rc, "gjkepa_collide_moving_patches")
+        n = int(ne[0])
+        if n <= cap or max_events is not None:
+            m = min(n, cap)
+            return {"events": ev[:m], "patches": patches[:m], "n_events": n, "counts": counts,
+                    "n_candidates": int(ncand[0]), "body_time": btime,
+                    "posed": HullPool(posed, pool.hull_off, pool.hull_cnt, pool.pairs) if pose else None}
         cap = n
 
 

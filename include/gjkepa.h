@@ -814,6 +814,7 @@ int gjkepa_collide_moving(int32_t version, double tol_ff, int32_t vert_dtype, in
 #define GJKEPA_MANIFOLD_NO_HIT    1   /* not computed: the contact record is no usable collision */
 #define GJKEPA_MANIFOLD_DECIMATED 2   /* a feature had more than GJKEPA_MANIFOLD_MAX_FEATURE vertices */
 #define GJKEPA_MANIFOLD_FALLBACK  4   /* no candidate: the one point is the projected collision_point */
+#define GJKEPA_MANIFOLD_AT_TOI    8   /* built from a cast record, on the hulls posed at its toi (gjkepa_manifold_cast_batch) */
 typedef struct gjkepa_manifold_f64 {
     double   depth;
     double   normal[3];
@@ -853,6 +854,87 @@ int gjkepa_manifold_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_
                           const int32_t* pairs, int64_t n_pairs,
                           const void* records, int32_t records_precision, double margin,
                           void* out, int32_t device);
+
+/* ---- contact manifold at the time of impact: the patch of a moving step's events -----------------
+ * The manifold above for the pairs a cast found: the patch of the two hulls posed at the pair's own time of
+ * impact, along the cast record's normal, so a box that lands flat on a floor during the step reaches the
+ * solver as four points and not as one witness point.  Inputs: the pool, a pair list, its n_pairs cast
+ * records (gjkepa_cast_f64 of gjkepa_cast_rigid_batch), body_motion (9 doubles per hull: the blocks the cast
+ * ran with), margin as above, and optionally the batch's contact records of the same list.  Output: one
+ * gjkepa_manifold_f64 per pair, in pair order.  Per pair the first rule that applies wins:
+ *   1. a hull count outside 1 .. GJKEPA_MAX_HULL_VERTS: GJKEPA_STATUS_BAD_INPUT (zeroed fields, codes
+ *      0xFFFFFFFF, no flag).
+ *   2. cast flag GJKEPA_CAST_SKIPPED: with records given, the pair is answered exactly as
+ *      gjkepa_manifold_batch_device answers it from that contact record (n = collision_normal, the unposed
+ *      hulls, fallback point collision_point): the same bytes; the motion blocks are not read.  With
+ *      records == NULL: GJKEPA_MANIFOLD_NO_HIT.
+ *   3. cast status GJKEPA_STATUS_BAD_INPUT: BAD_INPUT as in rule 1.
+ *   4. cast status GJKEPA_STATUS_CAST_MAXITER: NO_HIT.
+ *   5. flag GJKEPA_CAST_IMPACT or _START with a finite normal that is not zero: computed.  A non-finite vertex
+ *      of either hull, a non-finite value among the pair's 18 motion doubles, or a toi that is NaN or outside
+ *      [0, 1] gives BAD_INPUT.  (An overlapping START has a zero normal: rule 6.)
+ *   6. anything else (a MISS): NO_HIT.
+ * A computed pair runs steps 1 to 8 of the definition above unchanged, on these inputs:
+ *   vertices   vertex i of hull X is pose_point(pose_state(v_X, w_X, t), c_X, p_i) with t = the record's toi
+ *              (a START has toi 0), the arithmetic of csrc/rigid_pose.h as written: bit for bit what
+ *              gjkepa_pose_pool with out_dtype GJKEPA_DTYPE_F64 gives for that hull at that time.
+ *   normal     n = (-normal.x, -normal.y, -normal.z) of the cast record, negated exactly: the cast's normal
+ *              points from B to A, the manifold's from A into B (depth = hA - hB).
+ *   fallback   step 6's point is the cast record's point_a.
+ * depth is then minus the support gap along the normal: <= 0, and at least -tolerance for a record the cast
+ * certified.  The points lie on A's support plane at the time of impact, the partner on B is point - depth n,
+ * and the codes hold unposed vertex indices, so they stay stable from frame to frame.  Flags are the
+ * manifold's, plus GJKEPA_MANIFOLD_AT_TOI on every record computed from a cast record (rule 5); the records
+ * of rule 2 carry what gjkepa_manifold_batch gives them.
+ * A linear cast's records (gjkepa_cast_batch) are served by motion blocks with w = 0, v_A = 0 and v_B = the
+ * pair's relative motion; a body that is in several linear-cast pairs with different relative motions has no
+ * single block and is out of scope.
+ * Limit.  Two bodies that the per-body clamp (gjkepa_events_device) stops at different times are not at
+ * their pair's toi when posed at body_time; the patch describes the pair at its own toi, and what to do about
+ * the difference is the caller's policy. */
+/* Bytes of device workspace (as gjkepa_manifold_workspace_bytes); negative for n_pairs < 0. */
+int64_t gjkepa_manifold_cast_workspace_bytes(int64_t n_pairs);
+/* Device buffers, asynchronous on `stream`: the contract of gjkepa_manifold_batch_device (no allocation, no
+ * synchronisation, one stream, three tier launches after the counter reset, deterministic, nothing recorded
+ * for gjkepa_launch_timing; n_pairs == 0 returns 0).  body_motion (device, 9 doubles per hull of the pool) and
+ * cast_records (device, n_pairs gjkepa_cast_f64) are required; records: NULL, or the list's contact records.
+ * GJKEPA_E_ARG for a bad dtype, a bad records_precision with records != NULL, a margin that is NaN, infinite
+ * or negative, or a null required pointer; GJKEPA_E_WORKSPACE for a workspace below
+ * gjkepa_manifold_cast_workspace_bytes. */
+int gjkepa_manifold_cast_batch_device(int32_t vert_dtype, const void* verts, const int64_t* hull_off,
+                                      const int32_t* hull_cnt, const int32_t* pairs, int64_t n_pairs,
+                                      const double* body_motion, const void* cast_records,
+                                      const void* records, int32_t records_precision, double margin,
+                                      void* out, void* workspace, int64_t workspace_bytes, void* stream);
+/* Host buffers, blocking; the pool arguments and checks of gjkepa_cast_rigid_batch.  body_motion: 9 n_hulls
+ * doubles; cast_records: n_pairs records; records: NULL or n_pairs contact records (host memory). */
+int gjkepa_manifold_cast_batch(int32_t vert_dtype, const void* verts, int64_t n_vert_scalars,
+                               const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                               const int32_t* pairs, int64_t n_pairs,
+                               const double* body_motion, const void* cast_records,
+                               const void* records, int32_t records_precision, double margin,
+                               void* out, int32_t device);
+/* The manifolds of an event list: out[k] = manifolds[events[k].pair] for k < min(*n_events, max_events);
+ * nothing is written at or past that bound.  events, n_events (device int64), max_events: what
+ * gjkepa_events_device left; manifolds: the gjkepa_manifold_f64 records of the same pair list; out: room for
+ * max_events records.  Asynchronous on `stream`, one launch, no allocation (graph-capturable).  max_events == 0
+ * returns 0.  GJKEPA_E_ARG for a negative max_events or a null pointer. */
+int gjkepa_event_manifolds_device(const void* events, const int64_t* n_events, int64_t max_events,
+                                  const void* manifolds, void* out, void* stream);
+/* gjkepa_collide_moving with a patch per event (host buffers, blocking): after the event pass,
+ * gjkepa_manifold_cast_batch_device on the candidate list with the batch's records, then
+ * gjkepa_event_manifolds_device.  Every output it shares with gjkepa_collide_moving holds that call's bytes;
+ * patches (room for max_events gjkepa_manifold_f64) [k] belongs to events[k]: a HIT event gets its contact
+ * manifold, a START or IMPACT event the manifold at its time, an UNDECIDED event NO_HIT.  margin as for
+ * gjkepa_manifold_batch.  GJKEPA_E_ARG also for a bad margin or, with max_events > 0, patches == NULL. */
+int gjkepa_collide_moving_patches(int32_t version, double tol_ff, int32_t vert_dtype, int32_t precision,
+                                  const void* verts, int64_t n_vert_scalars,
+                                  const int64_t* hull_off, const int32_t* hull_cnt, int64_t n_hulls,
+                                  const double* body_motion, double tolerance, double long_radius,
+                                  void* events, int64_t max_events, int64_t* n_events,
+                                  int64_t* counts, int64_t* n_candidates,
+                                  double* body_time, void* verts_out, double margin, void* patches,
+                                  int32_t device);
 
 /* ---- whole collision step (host buffers, blocking) ---------------------------------------------
  * The reference caller's `DO a; DO b = a+1; CALL GJKEPA(...)` over a pooled hull set in one call:
