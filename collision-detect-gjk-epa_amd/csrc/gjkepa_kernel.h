@@ -65,7 +65,11 @@
 #define GJKEPA_E0_MINW 3        // with GJKEPA_E0_LH: 168 VGPRs; with the packed horizon list the LDS holds 12 waves/CU
 #endif
 #ifndef GJKEPA_E0_REFILL
-#define GJKEPA_E0_REFILL 2      // refill a wave's groups once this many are idle (0: per-round kernel)
+#define GJKEPA_E0_REFILL 1      // refill a wave's groups once this many are idle (0: per-round kernel); 2 until the
+                                // queue handed out pair metadata from LDS ("Pair metadata from LDS")
+#endif
+#ifndef GJKEPA_EPA_META
+#define GJKEPA_EPA_META 64      // refill tiers: most pairs whose metadata the queue loads at once (MetaTab: what the LDS block leaves)
 #endif
 #ifndef GJKEPA_E1_G
 #define GJKEPA_E1_G 32

@@ -2525,43 +2525,114 @@ __global__ __launch_bounds__(64, MINW) void epa_kernel(const gjkepa_epa_args a) 
     GK_STAMP_END();
 }
 
+// Pair metadata (hull counts and vertex offsets, groups_take's PairMeta) of the next TN routed pairs of a
+// chunk, in the wave's LDS behind the groups' images.  The hardware allots a workgroup's LDS in blocks of
+// 1,280 B (measured: a one-wave workgroup of 12,800 B is resident twelve times per CU, one of 12,864 B
+// eleven times, whatever the occupancy query answers), so the table takes what the images and the route
+// tallies leave of the wave's last block and never costs a tier a wave: EPA tier 0 <float, double> has
+// 12,224 B of 12,800, room for 24 entries: 23 pairs and the queue's own state, which takes one entry's
+// place behind them (<double, double>: 64 B left, one pair and the state).  Where fewer than two entries
+// are left the wave takes one more block (tiers 1 and 2, whose two waves per SIMD leave LDS to spare).
+struct MetaEnt { int64_t o[2]; int32_t n[2]; };       // vertex offsets and counts of hulls A, B
+struct QState { int64_t p0; uint64_t m; int32_t left; uint32_t next; };
+static_assert(sizeof(QState) == sizeof(MetaEnt), "the state stands in an entry's place");
+constexpr size_t kLdsBlock = 1280;
+template <typename L_t, int G> struct MetaTab {
+    static constexpr size_t AT = lds_stride<L_t, G>() * (64 / G);         // behind the images
+    static constexpr size_t USED = AT + sizeof(uint32_t) * GJKEPA_WS_TALLY;
+    static constexpr size_t FREE = (USED + kLdsBlock - 1) / kLdsBlock * kLdsBlock - USED;
+    static constexpr size_t FIT = (FREE < 2 * sizeof(MetaEnt) ? FREE + kLdsBlock : FREE) / sizeof(MetaEnt);
+    static constexpr int TN = FIT - 1 < (size_t)GJKEPA_EPA_META ? (int)FIT - 1 : GJKEPA_EPA_META;
+    static constexpr size_t BYTES = AT + (TN + 1) * sizeof(MetaEnt);     // the launch's dynamic LDS
+    static_assert(AT % 8 == 0 && TN > 0 && TN <= 64, "8-byte entries; one lane loads one entry");
+    MetaEnt* ent;
+    DEV explicit MetaTab(unsigned char* smem) : ent(reinterpret_cast<MetaEnt*>(smem + AT)) {}
+    DEV MetaEnt& operator[](int e) const { return ent[e]; }
+    DEV QState* state() const { return reinterpret_cast<QState*>(ent + TN); }
+};
+
 // Wave-uniform queue of the pairs routed to a launch, one work unit at a time (first unit
-// static, later ones from the launch counter as in for_each_routed_pair).
-struct PairQueue {
-    const uint8_t* route;
-    Units U;
-    int64_t ch, p0;
-    uint32_t* ctr;
+// static, later ones from the launch counter as in for_each_routed_pair).  The metadata of a
+// chunk's routed pairs is loaded TN pairs at once (lane l: the l-th routed pair left in the chunk, the
+// three dependent levels pair -> hull -> count / offset of all of them in flight together, as in
+// groups_take<G, META>) into the wave's MetaTab, so a refill waits on one level of loads (the
+// vertices).  The table is filled only at the top of a refill (begin()), never between two pops of
+// one: the groups refilled together read their entries after the last pop.  A refill that empties the
+// table hands out no further pair; the groups left idle take theirs at the next one.
+template <typename Tab, int G, int SMALL> struct PairQueue {
+    static constexpr int TN = Tab::TN;
+    // EPA tier 0 has no scalar register to spare across its loop (three waves per SIMD: one more spilled
+    // lane takes a second VGPR): the queue keeps no copies of its pointers, works the launch's units out
+    // again for every unit it takes, and its state rests in LDS (QState) between two refills
+    const gjkepa_epa_args& a;
+    const Tab tab;
+    int64_t p0;
     uint32_t next;
     uint64_t m;
-    int code;
+    int left;                   // entries left - 1 .. 0 of the table are the next pairs of m, in that order
     bool done;
-    DEV void load_chunk() {
+    DEV void wake() {
+        const QState s = *tab.state();
+        p0 = ((int64_t)__builtin_amdgcn_readfirstlane((int)(s.p0 >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)s.p0);
+        m = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(s.m >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)s.m);
+        left = __builtin_amdgcn_readfirstlane(s.left);
+        next = (uint32_t)__builtin_amdgcn_readfirstlane((int)s.next);
+    }
+    DEV void rest() {
+        if (lane_id() == 0) *tab.state() = QState{p0, m, left, next};
+        __builtin_amdgcn_wave_barrier();
+    }
+    // routed pairs of unit ch; false: the launch has no such unit
+    DEV bool load_chunk(int64_t ch) {
+        const Units U(a.n_pairs, tail_unit<G, SMALL>(a.n_pairs));
+        if (ch >= U.nunits) return false;
+        uint32_t claimed = 0;                                   // the unit after this one, beside the route bytes
+        if (lane_id() == 0) claimed = gridDim.x + atomicAdd(a.ctr, 1u);
         int len;
         U.range(ch, p0, len);
         const int64_t p = p0 + lane_id();
-        m = __ballot(lane_id() < len && (int)route[p] == code);
+        m = __ballot(lane_id() < len && (int)a.route[p] == a.route_code);
+        next = (uint32_t)__builtin_amdgcn_readfirstlane((int)claimed);
+        return true;
     }
-    DEV PairQueue(const uint8_t* route_, int64_t n, int small, int code_, uint32_t* ctr_)
-        : route(route_), U(n, small), ch(blockIdx.x), p0(0), ctr(ctr_), next(0), m(0), code(code_), done(false) {
-        if (ch < U.nunits) {
-            if (lane_id() == 0) next = gridDim.x + atomicAdd(ctr, 1u);
-            load_chunk();
-        } else {
-            done = true;
+    // lane l < n: the l-th routed pair still in m (pairs leave in order) into entry n - 1 - l
+    DEV void stage(int n) {
+        const int l = lane_id();
+        uint64_t mm = l < n ? m : 0;
+        for (int j = 0; j < l && mm; ++j) mm &= mm - 1;
+        if (mm) {
+            const int32_t* hp = a.pairs + 2 * (p0 + (int)__builtin_ctzll(mm));
+            MetaEnt& ent = tab[n - 1 - l];
+            // one hull after the other: few registers are free here, and a fill serves many refills
+#pragma nounroll
+            for (int s = 0; s < 2; ++s) {
+                const int32_t h = hp[s];
+                ent.o[s] = a.hull_off[h];
+                ent.n[s] = a.hull_cnt[h];
+            }
         }
+        __builtin_amdgcn_wave_barrier();
     }
-    // next pair in order, -1 when the launch has no more
+    DEV PairQueue(const gjkepa_epa_args& a_, Tab tab_) : a(a_), tab(tab_), p0(0), next(0), m(0), left(0), done(false) {
+        done = !load_chunk(blockIdx.x);
+        rest();
+    }
+    // top of a refill: an empty table takes the next pairs of the chunk, or of the next unit that has any
+    DEV void begin() {
+        wake();
+        if (left) return;
+        while (!m && !done) done = !load_chunk(next);
+        if (!m) return;
+        const int n = popc(m);
+        left = n < TN ? n : TN;
+        stage(left);
+    }
+    // next pair in order (its metadata: entry `left` after the call), -1 when the table is empty
     DEV int64_t pop() {
-        while (!m && !done) {
-            ch = (int64_t)__builtin_amdgcn_readfirstlane(next);
-            if (ch >= U.nunits) { done = true; break; }
-            if (lane_id() == 0) next = gridDim.x + atomicAdd(ctr, 1u);
-            load_chunk();
-        }
-        if (!m) return -1;
+        if (!left) return -1;
         const int bit = (int)__builtin_ctzll(m);
         m &= m - 1;
+        --left;
         return p0 + bit;
     }
 };
@@ -2580,6 +2651,7 @@ __global__ __launch_bounds__(64, MINW) void epa_kernel_refill(const gjkepa_epa_a
     constexpr int R = (FC + G - 1) / G;
     constexpr int NG = 64 / G;
     using L_t = Lds<T, TIn, G, K, VC, FC>;
+    using Tab_t = MetaTab<L_t, G>;
     extern __shared__ __align__(16) unsigned char smem[];
     const Grp<G> grp;
     L_t& L = *reinterpret_cast<L_t*>(smem + lds_stride<L_t, G>() * (grp.lane / G));
@@ -2595,7 +2667,7 @@ __global__ __launch_bounds__(64, MINW) void epa_kernel_refill(const gjkepa_epa_a
     if (a.route_code == GJKEPA_ROUTE_EPA0 + 1) __builtin_amdgcn_s_setprio(GJKEPA_E1_PRIO);
 #endif
     tally_begin();
-    PairQueue q(a.route, a.n_pairs, tail_unit<G, (2 * NG > 8 ? 2 * NG : 8)>(a.n_pairs), a.route_code, a.ctr);
+    PairQueue<Tab_t, G, (2 * NG > 8 ? 2 * NG : 8)> q(a, Tab_t(smem));
     Ctx<T, TIn, G, K, VC, FC, LH> c{L, grp};
     EpaState<T, R> S;
     bool active = false;
@@ -2630,27 +2702,30 @@ __global__ __launch_bounds__(64, MINW) void epa_kernel_refill(const gjkepa_epa_a
         const uint64_t idle = __ballot(gl == 0 && !active);
         const int nidle = popc(idle);
         bool fresh = false;
+        int e = 0;                           // the fresh pair's table entry
         if (!q.done && (nidle >= REFILL || nidle == NG)) {
+            q.begin();
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
                 if ((idle >> (g * G)) & 1ull) {
                     const int64_t p = q.pop();
-                    if (p >= 0 && gid == g) { pair = p; fresh = true; }
+                    if (p >= 0 && gid == g) { pair = p; fresh = true; e = q.left; }
                 }
             }
+            q.rest();
         }
         if (!__ballot(active || fresh)) break;
         GK_STAMP(SE_ROUTE);
         if (fresh) {
-            const int32_t ha = a.pairs[2 * pair], hb = a.pairs[2 * pair + 1];
-            c.na = a.hull_cnt[ha];
-            c.nb = a.hull_cnt[hb];
+            const MetaEnt& pm = q.tab[e];
+            c.na = pm.n[0];
+            c.nb = pm.n[1];
             const uint32_t* slot = reinterpret_cast<const uint32_t*>(a.out) + pair * (sizeof(T) == 8 ? 32 : 16);
             uint32_t kc[4];
             kc[0] = slot[0]; kc[1] = slot[1]; kc[2] = slot[2]; kc[3] = slot[3];
             gjk_it = slot[4];
             const SeedIn<T> seed = load_seed<T>(slot, gl);
-            load_hulls(c, verts + a.hull_off[ha], verts + a.hull_off[hb]);
+            load_hulls(c, verts + pm.o[0], verts + pm.o[1]);
             S.iters = 1; S.nf = 0;
             int r = ST_DEFER;
             seeded = false;
@@ -3893,7 +3968,9 @@ hipError_t launch_epa(const gjkepa_epa_args& a, hipStream_t s) {
         else return gk::epa_kernel<TIn, T, G, K, VC, FC, MINW, LH, PR>;
     }();
     constexpr int GPW = 64 / G;
-    const size_t lds = gk::lds_stride<gk::Lds<T, TIn, G, K, VC, FC>, G>() * GPW;
+    using L_t = gk::Lds<T, TIn, G, K, VC, FC>;
+    // the refill tiers keep their queue's pair metadata behind the images
+    const size_t lds = REFILL > 0 ? gk::MetaTab<L_t, G>::BYTES : gk::lds_stride<L_t, G>() * GPW;
     int grid = grid_for(kfn, lds, a.num_cus, a.grid);
     grid = grid_cap<G>(a.n_pairs, grid);
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(64), lds, s, a);
